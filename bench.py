@@ -4,7 +4,10 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches
 one rank per GPU through torch.distributed.run (RCCL).  W untimed warm-up steps, then exactly K
 timed steps bracketed by barrier + torch.cuda.synchronize() on both sides, MAX over ranks; rank 0
-prints ONE JSON line.
+prints ONE JSON line.  Such a plain run does only that (set-up, warm-up, the timed steps, the line); `--full` adds
+every other figure and check below (self-checks, window T2, the per-kernel pass, other call orders, the logical-shard
+projection, the cpu_baseline legs, the configs[1]/[3]/[4] sub-records).  `--dump-outputs DIR` writes what the last
+timed step computed as DIR/<name>.npy (single GPU; the inputs are seeded, so runs of two builds compare array for array).
 
 Workload (BASELINE.json `metric`: "Merkle proofs verified/sec + HBM GB/s, 1M-receipt synthetic
 tipset"): configs[2]'s tipset — 1 000 000 receipts under an Amtv0<Receipt>, one events AMT
@@ -251,6 +254,89 @@ def make_cfg2(n: int, seed: int):
     return data.reshape(-1), off, lens
 
 
+# ---- --dump-outputs ----------------------------------------------------------------------------------------------
+# What the timed path computed in its last step, as a caller of that path receives it, one DIR/<name>.npy per array:
+# integers are written as float32 (below 2^24) or float64 (below 2^53), so every value is exact.  The inputs are seeded,
+# so two builds run with the same arguments can be compared array for array.
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _exact_float(a, dtype):
+    a = np.asarray(a)
+    limit = 2 ** 24 if dtype == np.float32 else 2 ** 53
+    if a.size and int(a.max()) >= limit:
+        raise SystemExit("bench.py --dump-outputs: a value does not fit %s exactly" % np.dtype(dtype).name)
+    return a.astype(dtype)
+
+
+def dump_outputs(dirname, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def tipset_outputs(w, t_status, t_has, t_matches, scan_result):
+    """The tipset step's product after the timed steps: a status byte per claim, the scan's has-match map and match
+    records (left in HBM by the step), its status and match count, and the K1 verdict of every witness block."""
+    import ipc_filecoin_proofs_amd as ipcfp
+
+    n_matches = int(scan_result["matches"])
+    rec = t_matches.cpu().numpy()[: min(n_matches, MATCH_CAP) * MATCH_BYTES].view(ipcfp.MATCH_DTYPE)
+    cid_status, _ = w.cid_results()  # the last step's K1 (waits for it, launches nothing)
+    return {
+        "claim_status": _exact_float(t_status.cpu().numpy(), np.float32),
+        "receipt_has_match": _exact_float(t_has.cpu().numpy(), np.float32),
+        "matches": _exact_float(np.stack([rec[f] for f in ("exec_index", "event_index", "emitter", "block", "off", "len")], axis=1)
+                                .reshape(-1, 6), np.float64),
+        "scan": _exact_float(np.array([scan_result["status"], n_matches]), np.float64),
+        "cid_status": _exact_float(cid_status, np.float32),
+    }
+
+
+def tipset_record(args, tip, info, world, n_claims, total_claims, elapsed, scan_matches, t_gen, roof):
+    """The single-GPU tipset report: the contract's keys, the config and K1's roofline from the timed steps."""
+    return {
+        "metric": METRIC,
+        "value": total_claims * args.steps / elapsed,
+        "unit": "proofs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",  # (N = 1: neither cut applies; config.sharding says what --gpus N does)
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic",
+        "config": {
+            "workload": "BASELINE.json configs[2] (the 1M-receipt tipset the metric is quoted on): %d receipts (Amtv0<Receipt> + one Amt<StampedEvent> each, 5 parent "
+                        "headers with TxMeta and message AMTs), %d witness blocks, %.3f GB; one EventProof claim per "
+                        "receipt; step = CID index + Blake2b-256 CID check of every block + exec-order reconstruction + "
+                        "verify_event_proof of every claim + event-filter scan (has-match map and match records delivered in "
+                        "HBM); verify and scan in one ABI call (ipcfp_verify_and_scan_device) unless --separate-calls" %
+                        (args.receipts, tip.n_blocks, tip.stats["payload_bytes"] / 1e9),
+            "receipts_per_gpu": args.receipts,
+            "claims_per_gpu": n_claims,
+            "witness_blocks_per_gpu": tip.n_blocks,
+            "witness_bytes_per_gpu": tip.stats["payload_bytes"],
+            "scan_matches": int(scan_matches),
+            "sharding": "single GPU.  --gpus N cuts THIS ONE tipset by receipt range over N ranks (strong scaling: the line's `value`), every "
+                        "rank a self-planned shard (ipcfp_witness_create_shard_pull: the device follows the links and reads its blocks out of "
+                        "the bundle in registered host memory), one ncclAllGather of [header | status bytes | has-match map | CID bitmap]; "
+                        "with --full, `scaling_projection` times every such shard by itself on this GPU with plan, cut, claims, upload, verify "
+                        "and scan inside ONE T2 figure; --shard tipsets runs one tipset per rank instead (weak scaling, a sub-record)",
+            "device": info["name"],
+            "setup_seconds_untimed": round(t_gen, 2),
+        },
+        "roofline": roof,
+        "window": "T3 (inputs resident in HBM; index rebuilt and every cached enumeration dropped each step)",
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -284,7 +370,18 @@ def main():
                     help="only the timed steps: no per-kernel pass, no `alone` K1 launches, no other call order, no "
                          "gather-message step (what the profiler scripts trace)")
     ap.add_argument("--sub-steps", type=int, default=5, help="timed steps of each compact sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: self-checks, the T2 window, the per-kernel pass, other call orders, "
+                         "the logical-shard projection, the cpu_baseline legs and the configs[1]/[3]/[4] sub-records.  Without it a "
+                         "run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run measures the headline and nothing else: every extra figure and check is --full's
+        args.no_cpu_baseline, args.no_sub_records, args.plain, args.t2_reps, args.logical_shards = True, True, True, 0, ""
 
     import torch
     import torch.distributed as dist
@@ -299,6 +396,8 @@ def main():
         raise SystemExit("bench.py needs an MI355X: the engine has no CPU path")
     torch.cuda.set_device(local_rank)
     dev = f"cuda:{local_rank}"
+    if args.dump_outputs and (world > 1 or args.force_sharded):
+        raise SystemExit("bench.py: --dump-outputs is for single-GPU runs (no --gpus N > 1, no --force-sharded)")
     if world > 1 or args.force_sharded:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -430,6 +529,16 @@ def main():
         tc = torch.tensor([n_claims], dtype=torch.int64, device=dev)
         dist.all_reduce(tc, op=dist.ReduceOp.SUM)
         total_claims = int(tc.item())
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, tipset_outputs(w, t_status, t_has, t_matches, scan_result))
+    if not args.full:
+        out = tipset_record(args, tip, info, world, n_claims, total_claims, elapsed, scan_result["matches"], t_gen,
+                            k1_roofline(eng, tip.lens, tip.n_blocks, with_traffic=True, timed=k1_timed))
+        w.close()
+        emit(out)
+        eng.close()
+        return
 
     # ---- what was timed must be right (self-check; parity proper lives in tests/) ----
     status = t_status.cpu().numpy()
@@ -594,50 +703,15 @@ def main():
                 extras["ms_per_step_with_gather_message"], t2["ms_per_tipset"] if t2 else None,
                 shard_counts=tuple(int(x) for x in args.logical_shards.split(",")), steps=args.sub_steps)
     if rank == 0:
-        out = {
-            "metric": METRIC,
-            "value": total_claims * args.steps / elapsed,
-            "unit": "proofs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",  # (N = 1: neither cut applies; config.sharding says what --gpus N does)
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {
-                "workload": "BASELINE.json configs[2] (the 1M-receipt tipset the metric is quoted on): %d receipts (Amtv0<Receipt> + one Amt<StampedEvent> each, 5 parent "
-                            "headers with TxMeta and message AMTs), %d witness blocks, %.3f GB; one EventProof claim per "
-                            "receipt; step = CID index + Blake2b-256 CID check of every block + exec-order reconstruction + "
-                            "verify_event_proof of every claim + event-filter scan (has-match map and match records delivered in "
-                            "HBM); verify and scan in one ABI call (ipcfp_verify_and_scan_device) unless --separate-calls" %
-                            (args.receipts, tip.n_blocks, tip.stats["payload_bytes"] / 1e9),
-                "receipts_per_gpu": args.receipts,
-                "claims_per_gpu": n_claims,
-                "witness_blocks_per_gpu": tip.n_blocks,
-                "witness_bytes_per_gpu": tip.stats["payload_bytes"],
-                "scan_matches": int(scan_result["matches"]),
-                "sharding": "single GPU.  --gpus N cuts THIS ONE tipset by receipt range over N ranks (strong scaling: the line's `value`), every "
-                            "rank a self-planned shard (ipcfp_witness_create_shard_pull: the device follows the links and reads its blocks out of "
-                            "the bundle in registered host memory), one ncclAllGather of [header | status bytes | has-match map | CID bitmap]; "
-                            "`scaling_projection` below times every such shard by itself on this GPU with plan, cut, claims, upload, verify and scan "
-                            "inside ONE T2 figure; --shard tipsets runs one tipset per rank instead (weak scaling, a sub-record)",
-                "device": info["name"],
-                "setup_seconds_untimed": round(t_gen, 2),
-            },
-            "roofline": roof,
-            "kernels": kernels,
-            "kernels_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in kern.items()},
-        }
+        out = tipset_record(args, tip, info, world, n_claims, total_claims, elapsed, scan_result["matches"], t_gen, roof)
+        out["kernels"] = kernels
+        out["kernels_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in kern.items()}
         if t2 is not None:
             out["value_T2"] = t2["value"]
             out["window_T2"] = t2
             # (a driver that keeps only the contract's keys keeps nested dicts: the window the >= 10x claim is judged on rides in `config`)
             out["config"]["window_T2"] = {"proofs_per_s": t2["value"], "ms_per_tipset": t2["ms_per_tipset"], "h2d_bytes": t2.get("h2d_bytes"),
                                           "what": "the same pass from pageable HOST memory (PCIe-inclusive: upload, index, K1, verify, scan, results back)"}
-        out["window"] = "T3 (inputs resident in HBM; index rebuilt and every cached enumeration dropped each step)"
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(tip, status, args.cpu_sample, args.cpu_sample_mt, cid_status, gpu_scan)
             cb = out["cpu_baseline"]
@@ -660,7 +734,7 @@ def main():
             # BASELINE.json configs[1], [3], [4] in the SAME driver-visible line: compact records, each with its own
             # `roofline` and `cpu_baseline` (bounded samples)
             sub_args = argparse.Namespace(**vars(args))
-            sub_args.steps, sub_args.warmup = args.sub_steps, 2
+            sub_args.steps, sub_args.warmup, sub_args.dump_outputs = args.sub_steps, 2, None
             state = _state_tipset()
             out["configs"] = {
                 "configs[1] cid": compact(run_cid(sub_args, eng, info, torch, ranks)),
@@ -1448,6 +1522,8 @@ def run_cid(args, eng, info, torch, ranks):
 
     elapsed = timed(ranks, step, args.steps, args.warmup)
     st, nbad = w.cid_results()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"cid_status": _exact_float(st, np.float32)})
     if nbad != len(flipped_local) or not (st[flipped_local] == 0).all() or int(st.sum()) != m - len(flipped_local):
         raise SystemExit("bench self-check failed: CID verdicts")
     if world > 1:  # every rank checks the WHOLE batch's gathered bitmap
@@ -1545,6 +1621,9 @@ def run_hamt(args, eng, info, torch, ranks, state=None):
     present = T.query_present.astype(bool)
     want = np.where(present, 1, 32).astype(np.uint8)
     gs = d_st.cpu().numpy()[:m]
+    if args.dump_outputs:
+        loc = d_loc.cpu().numpy()[: m * 12].view(np.uint32).reshape(m, 3)  # (block, off, len) of every value found
+        dump_outputs(args.dump_outputs, {"get_status": _exact_float(gs, np.float32), "locations": _exact_float(loc, np.float64)})
     if not np.array_equal(gs, want[lo:hi]):
         raise SystemExit("bench self-check failed: actor gets")
     if world > 1:
@@ -1629,6 +1708,8 @@ def run_storage(args, eng, info, torch, ranks, state=None):
     cnt, ms = eng.profile_read("storage_verify")
     k_avg_ms = ms / max(cnt, 1)
     got = d_st.cpu().numpy()[:m]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"claim_status": _exact_float(got, np.float32)})
     if not np.array_equal(got, want[lo:hi]):
         raise SystemExit("bench self-check failed: storage verdicts")
     if world > 1:

@@ -12,6 +12,7 @@ import math
 import os
 from contextlib import redirect_stdout
 
+import numpy as np
 import pytest
 
 import bench
@@ -155,3 +156,19 @@ def test_emit_prints_one_line_last_and_writes_the_report(tmp_path, monkeypatch):
         with open(where / "bench_detail.json") as f:
             full = json.load(f)
         assert len(full["scaling_projection"]["shards"]["8"]["per_shard"]) == 8  # the whole report is kept, off stdout
+
+
+def test_dump_outputs_are_exact_floats_and_bounded(tmp_path):
+    """--dump-outputs: integer results reach DIR/<name>.npy as float32 / float64 without rounding; a value that would
+    round, or a dump over 64 MB, is refused."""
+    arrays = {"status": bench._exact_float(np.array([0, 1, 21, 255], dtype=np.uint8), np.float32),
+              "index": bench._exact_float(np.array([2 ** 53 - 1], dtype=np.uint64), np.float64)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert np.load(tmp_path / "d" / "status.npy").tolist() == [0, 1, 21, 255]
+    back = np.load(tmp_path / "d" / "index.npy")
+    assert back.dtype == np.float64 and int(back[0]) == 2 ** 53 - 1
+    with pytest.raises(SystemExit):
+        bench._exact_float(np.array([2 ** 24], dtype=np.uint32), np.float32)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, dtype=np.float32)})
+    assert not os.path.exists(tmp_path / "big")

@@ -11,6 +11,6 @@ if [ -z "$SKIP_OLD" ]; then
 ( time timeout ${T_OLD:-420} python -m pytest tests -m gpu -x -v --timeout=200 -p no:cacheprovider --deselect tests/test_gpu_sharding.py --deselect tests/test_gpu_baseline_sizes.py 2>&1 | stamp ) > "$out/pytest_old.log" 2>&1
 tail -5 "$out/pytest_old.log"
 fi
-( time timeout 300 python bench.py --steps 20 --warmup 5 ) > "$out/bench.log" 2>&1; tail -c 3000 "$out/bench.log"
-( time timeout 200 python bench.py --steps 10 --warmup 3 --force-sharded ) > "$out/bench_sharded1.log" 2>&1; tail -c 1500 "$out/bench_sharded1.log"
-( time timeout 120 python bench.py --workload cid --steps 20 --warmup 3 ) > "$out/bench_cid.log" 2>&1; tail -c 1200 "$out/bench_cid.log"
+( time timeout 300 python bench.py --steps 20 --warmup 5 --full ) > "$out/bench.log" 2>&1; tail -c 3000 "$out/bench.log"
+( time timeout 200 python bench.py --steps 10 --warmup 3 --force-sharded --full ) > "$out/bench_sharded1.log" 2>&1; tail -c 1500 "$out/bench_sharded1.log"
+( time timeout 120 python bench.py --workload cid --steps 20 --warmup 3 --full ) > "$out/bench_cid.log" 2>&1; tail -c 1200 "$out/bench_cid.log"
