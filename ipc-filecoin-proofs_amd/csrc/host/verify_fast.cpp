@@ -192,28 +192,15 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     ex.mask = size - 1;
     ex.raw_len = n_msgs;
     IPCFP_HIP(ctx, ex.slots.alloc(size));
-    IPCFP_HIP(ctx, ex.first.alloc(n_msgs));
+    // the flags, and behind them (8-byte aligned) the look-back words of k_exec_scan_finish: cleared together
+    const size_t first_words = (size_t(n_msgs) + 1) & ~size_t(1), scan_ctl_words = exec_scan_ctl_words(n_msgs);
+    IPCFP_HIP(ctx, ex.first.alloc(first_words + 2 * scan_ctl_words));
     IPCFP_HIP(ctx, ex.pos.alloc(n_msgs));
     IPCFP_HIP(ctx, ex.inv.alloc(n_msgs));
-    const DenseClear clear{ex.slots.p, size, ex.first.p, n_msgs};
-    prof.reset(new ProfileScope(ctx, IPCFP_K_AMT_WALK));
-    // the receipt leaves are consumed on the aux stream (k_receipt_events), the message keys on the main stream: the two
-    // leaf kernels fork accordingly and run side by side (IPCFP_LEAVES_AUX=0: both on the main stream, one after the other)
-    static const bool leaves_aux = [] {
-        const char* e = std::getenv("IPCFP_LEAVES_AUX");
-        return !(e && std::atoi(e) == 0);
-    }();
-    rc = launch_dense_walk(ctx, view, dense_frontier.p, plan, a.p, b.p, nullptr, ex.keys.p, rleaves.p, small + 2,
-                           leaves_aux ? ctx->stream_aux : nullptr, leaves_aux ? ctx->main_event : nullptr,
-                           ctx->stream != swap.saved ? swap.saved : nullptr, ctx->narrow_event, ctx->narrow_max_wg, &clear);
-    if (rc) return rc;
-    // (the main stream now waits for everything the narrow stream was given: its small copies are the main stream's)
-    for (auto& r : ctx->pending)
-        if (ctx->stream_narrow && r.stream == ctx->stream_narrow) r.stream = ctx->stream;
-    if (prof) prof->stream = ctx->stream;  // (started on the narrow stream, ends on the main one)
-    prof.reset();
-    if (ctx->k1_defer == 1 && (rc = k1_flush(ctx, true))) return rc;
-    // the receipts' event records: aux stream, behind the block-order parse and behind the leaves just queued
+    unsigned long long* const scan_ctl = reinterpret_cast<unsigned long long*>(ex.first.p + first_words);
+    const DenseClear clear{ex.slots.p, size, ex.first.p, first_words + 2 * scan_ctl_words};
+    // the receipts' event records, written by the receipts tree's leaf kernel (k_dense_receipt_leaves) on the aux stream,
+    // behind the block-order parse: allocated, and the error word set, before the walk is queued
     std::unique_ptr<EventTableCached> table(new EventTableCached());
     table->lo = w->receipt_lo;
     table->hi = w->receipt_hi;
@@ -226,61 +213,40 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
         table->counts_filter = w->bt_filter;
         IPCFP_HIP(ctx, table->counts.alloc(n_rcpt));
     }
-    if (!leaves_aux) {  // (forked: the leaves are already on the aux stream, in order before what follows)
-        IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));
-        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
-    }
     IPCFP_HIP(ctx, hipMemsetAsync(table->err_word.p, 0xff, 8, ctx->stream_aux));  // kNoEnumError
-    rc = launch_receipt_events(ctx, view, rleaves.p, n_rcpt, table->has_counts ? &w->bt_filter.filter : nullptr,
-                               int(w->bt_filter.has_actor), w->bt_filter.actor, w->bt_blocks.p, table->receipts.p,
-                               table->has_counts ? table->counts.p : nullptr, table->err_word.p, ctx->stream_aux);
+    const DenseReceiptOut recs{w->bt_blocks.p, table->receipts.p, table->has_counts ? table->counts.p : nullptr, table->err_word.p};
+    prof.reset(new ProfileScope(ctx, IPCFP_K_AMT_WALK));
+    // the receipt leaves (and their records) are consumed on the aux stream, the message keys on the main stream: the two
+    // leaf kernels fork accordingly and run side by side
+    rc = launch_dense_walk(ctx, view, dense_frontier.p, plan, a.p, b.p, nullptr, ex.keys.p, rleaves.p, small + 2, ctx->stream_aux,
+                           ctx->main_event, ctx->stream != swap.saved ? swap.saved : nullptr, ctx->narrow_event, ctx->narrow_max_wg,
+                           &clear, &recs);
+    if (rc) return rc;
+    // (the main stream now waits for everything the narrow stream was given: its small copies are the main stream's)
+    for (auto& r : ctx->pending)
+        if (ctx->stream_narrow && r.stream == ctx->stream_narrow) r.stream = ctx->stream;
+    if (prof) prof->stream = ctx->stream;  // (started on the narrow stream, ends on the main one)
+    prof.reset();
+    if (ctx->k1_defer == 1 && (rc = k1_flush(ctx, true))) return rc;
+    // the receipts the table does not cover: the general walker, aux stream, right behind the leaves
+    rc = launch_receipt_walk(ctx, view, rleaves.p, n_rcpt, table->has_counts ? &w->bt_filter.filter : nullptr,
+                             int(w->bt_filter.has_actor), w->bt_filter.actor, table->receipts.p,
+                             table->has_counts ? table->counts.p : nullptr, table->err_word.p, ctx->stream_aux);
     if (rc) return rc;
     IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
     w->bt_joined = false;
-    if (defer_rehash) {  // behind the receipts' event records, which the verify kernel waits for — this it does not wait for
-        rc = launch_txmeta_rehash(ctx, ctx->stream_aux, view, tcs_d.p, ex.err.p);
-        if (rc) return rc;
-        IPCFP_HIP(ctx, hipEventRecord(ctx->rehash_event, ctx->stream_aux));
-    }
-    // the execution order: first-seen dedupe of the message CIDs, positions, inverse — main stream, beside the above
-    prof.reset(new ProfileScope(ctx, IPCFP_K_EXEC_ORDER));
-    // (table and flags were cleared by the walk's k_dense_link_leaves: launch_dense_walk `clear`)
-    rc = launch_exec_insert_flags(ctx, ex.keys.p, n_msgs, ex.slots.p, ex.mask, ex.first.p);
-    if (rc) return rc;
-    DevBuf<uint64_t> tiles;
-    IPCFP_HIP(ctx, tiles.alloc(size_t(div_up(n_msgs, 256)) + 2));
-    IPCFP_HIP(ctx, ctl_words(ctx, ex.total_own, ex.total.p, 1, false));
-    CtxFinish fin{};
-    fin.err = ex.err.p;
-    fin.total = ex.total.p;
-    fin.first = ex.first.p;
-    fin.pos = ex.pos.p;
-    fin.inv = ex.inv.p;
-    fin.slots = ex.slots.p;
-    fin.keys = ex.keys.p;
-    fin.mask = ex.mask;
-    fin.raw_len = n_msgs;
-    fin.receipt_leaves = rleaves.p;
-    fin.n_receipt_leaves = n_rcpt;
-    fin.receipt_first = w->receipt_lo;
-    fin.receipt_recs = table->receipts.p;
-    fin.event_recs = table->events;
-    rc = launch_exec_finish_fused(ctx, tcs_d.p, fin, ex.first.p, ex.pos.p, tiles.p, ex.total.p, /*flags_ready=*/true);
-    if (rc) return rc;
-    prof.reset();
-    rc = event_table_join(ctx, w);
-    if (rc) return rc;
-    if (ctx->k1_defer == 2 && (rc = k1_flush(ctx, true))) return rc;
-    if ((rc = claims_ready(ctx))) return rc;  // claims that were crossing PCIe beside all of the above are in HBM
-    rc = launch_verify_events(ctx, view, claims_d, n, tcs_d.p, 1, blob_d, blob_len, trust ? *trust : accept_all, filter, status_d,
-                              where_d, /*tabulated=*/true);
-    if (rc) return rc;
-    if ((rc = k1_flush(ctx, true))) return rc;  // (mode 3, and whatever is still noted)
-    // ---- a scan riding on this call (ipcfp_verify_and_scan_device): its tail right behind the verify kernel ----
+    // ---- a scan riding on this call (ipcfp_verify_and_scan_device): its tail on the aux stream, behind the receipt records
+    // and beside the verify kernel — it reads leaves, records and counts, never a claim's status ----
     DevBuf<uint32_t> ride_counts, ride_offsets;
     DevBuf<unsigned long long> ride_err_own;
     unsigned long long ride_seq = 0;
     if (ride && ctx->scan_fused != 0 && ride->cap_matches <= (1ull << 26) && (!ride->has_d || ride->cap_receipts >= n_rcpt)) {
+        struct OnAux {  // everything queued "on the call's stream" below goes to the aux stream
+            ipcfp_ctx* c;
+            hipStream_t saved;
+            ~OnAux() { c->stream = saved; }
+        } on_aux{ctx, ctx->stream};
+        ctx->stream = ctx->stream_aux;
         const ScanParams want = scan_params_of(ride->filter, ride->has_actor, ride->actor);
         const EventTableView tview = table->view();
         const uint32_t* cnt = nullptr;
@@ -309,7 +275,50 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
         ctx->scan_hint = want;
         ctx->has_scan_hint = true;
     }
-    if (defer_rehash) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->rehash_event, 0));  // its errors are in before the flags are read
+    if (defer_rehash) {  // behind the receipts' event records, which the verify kernel waits for — this it does not wait for
+        rc = launch_txmeta_rehash(ctx, ctx->stream_aux, view, tcs_d.p, ex.err.p);
+        if (rc) return rc;
+    }
+    // the execution order: first-seen dedupe of the message CIDs, positions, inverse — main stream, beside the above
+    prof.reset(new ProfileScope(ctx, IPCFP_K_EXEC_ORDER));
+    // (table and flags were cleared by the walk's k_dense_link_leaves: launch_dense_walk `clear`)
+    rc = launch_exec_insert_flags(ctx, ex.keys.p, n_msgs, ex.slots.p, ex.mask, ex.first.p);
+    if (rc) return rc;
+    IPCFP_HIP(ctx, ctl_words(ctx, ex.total_own, ex.total.p, 1, false));
+    CtxFinish fin{};
+    fin.err = ex.err.p;
+    fin.total = ex.total.p;
+    fin.first = ex.first.p;
+    fin.pos = ex.pos.p;
+    fin.inv = ex.inv.p;
+    fin.slots = ex.slots.p;
+    fin.keys = ex.keys.p;
+    fin.mask = ex.mask;
+    fin.raw_len = n_msgs;
+    fin.receipt_leaves = rleaves.p;
+    fin.n_receipt_leaves = n_rcpt;
+    fin.receipt_first = w->receipt_lo;
+    fin.receipt_recs = table->receipts.p;
+    fin.event_recs = table->events;
+    rc = launch_exec_scan_finish(ctx, tcs_d.p, fin, ex.pos.p, ex.total.p, scan_ctl);
+    if (rc) return rc;
+    prof.reset();
+    rc = event_table_join(ctx, w);  // (the receipt records: aux_event as recorded behind k_receipt_walk)
+    if (rc) return rc;
+    if (ctx->k1_defer == 2 && (rc = k1_flush(ctx, true))) return rc;
+    if ((rc = claims_ready(ctx))) return rc;  // claims that were crossing PCIe beside all of the above are in HBM
+    rc = launch_verify_events(ctx, view, claims_d, n, tcs_d.p, 1, blob_d, blob_len, trust ? *trust : accept_all, filter, status_d,
+                              where_d, /*tabulated=*/true);
+    if (rc) return rc;
+    if ((rc = k1_flush(ctx, true))) return rc;  // (mode 3, and whatever is still noted)
+    // the aux stream's tail — the re-hash, the riding scan — joins before the flags are read: its errors and the scan's
+    // results are in when the call's one synchronisation returns.  (Recorded only now: the join above took the earlier
+    // record, so the verify kernel does not wait for these.)
+    if (defer_rehash || ride_seq) {
+        hipEvent_t aux_done = defer_rehash ? ctx->rehash_event : ctx->aux_event;
+        IPCFP_HIP(ctx, hipEventRecord(aux_done, ctx->stream_aux));
+        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, aux_done, 0));
+    }
     // ---- the one synchronisation: did the dense walk hold? ----
     uint32_t bad = 0;
     unsigned long long e = kNoEnumError;
@@ -348,7 +357,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
         std::memcpy(table->root, facts.receipts_root.w, 40);
         w->table_cache.push_back(std::move(table));
     }
-    if (ride_seq) {  // (published before the synchronisation above returned: the tail ran ahead of it on the same stream)
+    if (ride_seq) {  // (published before the synchronisation above returned: the main stream joined the tail's stream)
         if (__atomic_load_n(ctx->mailbox, __ATOMIC_ACQUIRE) != ride_seq) return set_error(ctx, IPCFP_E_HIP, "the riding scan's results never reached the mailbox");
         const uint64_t nm = __atomic_load_n(ctx->mailbox + 1, __ATOMIC_RELAXED);
         unsigned long long e1 = __atomic_load_n(ctx->mailbox + 3, __ATOMIC_RELAXED);

@@ -87,6 +87,16 @@ struct DenseClear {
     uint32_t* words;            // n_words × 0
     uint64_t n_words;
 };
+// the extra root is a receipts tree and its leaves also write the receipts' event records (launch_dense_walk `receipts`):
+// what k_receipt_events writes, from k_dense_receipt_leaves — one lane per receipt, the receipt read once
+struct BlockRec;
+struct ReceiptRec;
+struct DenseReceiptOut {
+    const BlockRec* brecs;     // k_block_events' records, ordered before the leaves on their stream
+    ReceiptRec* rrecs;         // one per receipt of [lo, hi)
+    uint32_t* counts;          // nullable: matches of the table's filter (kWalkPending where the table does not cover)
+    unsigned long long* err;   // the missing events blocks' error word (kNoEnumError on entry)
+};
 void dense_plan(const std::vector<uint64_t>& root_info, uint32_t n_roots, int vkind, bool want_keys, uint64_t lo, uint64_t hi,
                 uint32_t has_extra, int extra_vkind, uint64_t extra_lo, uint64_t extra_hi, DensePlan& plan);
 int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* frontier, const DensePlan& plan,
@@ -97,7 +107,9 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
                       // than `narrow_max_wg` workgroups — the leaves at the latest — hands over to `wide_stream` through
                       // `wide_event`, and ctx->stream is `wide_stream` on return
                       hipStream_t wide_stream = nullptr, hipEvent_t wide_event = nullptr, uint32_t narrow_max_wg = 0,
-                      const DenseClear* clear = nullptr);
+                      const DenseClear* clear = nullptr,
+                      // non-null: the extra root's leaves take k_dense_receipt_leaves (a receipts tree), on the leaves' stream
+                      const DenseReceiptOut* receipts = nullptr);
 
 int launch_enum_roots(ipcfp_ctx* ctx, const WitnessView& view, const AmtRootSpec* roots_d, uint32_t n_all, int vkind,
                       EnumNode* frontier_d, uint32_t* max_height_d, unsigned long long* err_d, uint64_t* root_info_d,

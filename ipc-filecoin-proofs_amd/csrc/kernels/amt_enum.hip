@@ -9,6 +9,7 @@
 
 #include "../common.h"
 #include "blake2b_dev.h"
+#include "event_table.h"
 #include "launch.h"
 #include "tipset_ctx.h"
 
@@ -732,6 +733,158 @@ __global__ __launch_bounds__(256) void k_dense_leaves(WitnessView w, const Dense
     }
 }
 
+// Where the receipt value at `s` of a node ends, from its heads alone — `84 | exit code | return data | gas used | null or
+// tag 42 + bytes` in two dependent fetches of plain loads (the value's start, then the one behind the return data) — or 0
+// when it is not spelled so (the caller then takes the reader).  It decides nothing: every value is type-checked by a lane
+// of its node, which refuses what the reader refuses.  Reads stay within 32 bytes of a position inside the block (blocks
+// sit on 128-byte lines, the arena has 256 bytes of tail slack).
+__device__ __forceinline__ uint32_t receipt_end_fast(const uint8_t* node, uint32_t s, uint32_t rem) {
+    if (s >= rem) return 0;
+    const uint64_t a0 = load_u64_any(node + s), a1 = load_u64_any(node + s + 8), a2 = load_u64_any(node + s + 16);
+    auto ab = [&](uint32_t i) { return uint32_t((i < 8u ? a0 >> (8u * i) : (i < 16u ? a1 >> (8u * (i - 8u)) : a2 >> (8u * (i - 16u)))) & 0xffull); };
+    auto extra = [](uint32_t info) { return info < 24u ? 0u : (info == 24u ? 1u : (info == 25u ? 2u : (info == 26u ? 4u : (info == 27u ? 8u : 99u)))); };
+    if (ab(0) != 0x84u) return 0;
+    uint32_t b = ab(1);
+    uint32_t x = extra(b & 31u);
+    if ((b >> 5) != 0u || x > 8u) return 0;  // exit code: an unsigned integer
+    uint32_t p = 2u + x;
+    b = ab(p);  // the return data: a byte string of at most 2^32 - 1 bytes
+    x = extra(b & 31u);
+    if ((b >> 5) != 2u || x > 4u) return 0;
+    uint64_t len = b & 31u;
+    if (x == 1u) len = ab(p + 1u);
+    else if (x == 2u) len = (ab(p + 1u) << 8) | ab(p + 2u);
+    else if (x == 4u) len = (uint64_t(ab(p + 1u)) << 24) | (ab(p + 2u) << 16) | (ab(p + 3u) << 8) | ab(p + 4u);
+    const uint64_t g = uint64_t(s) + p + 1u + x + len;  // gas used
+    if (g >= rem) return 0;
+    const uint64_t c0 = load_u64_any(node + g), c1 = load_u64_any(node + g + 8);
+    auto cb = [&](uint32_t i) { return uint32_t((i < 8u ? c0 >> (8u * i) : c1 >> (8u * (i - 8u))) & 0xffull); };
+    b = cb(0);
+    x = extra(b & 31u);
+    if ((b >> 5) != 0u || x > 8u) return 0;
+    const uint32_t q = 1u + x;
+    uint64_t end;
+    if (cb(q) == 0xf6u) {
+        end = g + q + 1u;  // no events root
+    } else {
+        if (cb(q) != 0xd8u || cb(q + 1u) != 0x2au) return 0;  // tag 42
+        b = cb(q + 2u);
+        if ((b >> 5) != 2u || (b & 31u) > 24u) return 0;
+        end = (b & 31u) < 24u ? g + q + 3u + (b & 31u) : g + q + 4u + cb(q + 3u);
+    }
+    return end <= rem ? uint32_t(end) : 0u;
+}
+
+// Leaf level of the RECEIPTS tree on the verify call's table route (host/verify_fast.cpp): one lane per receipt VALUE, where
+// k_dense_leaves takes one lane per leaf node (its values decoded one after the other, 3.9 k wavefronts for 1 M receipts)
+// and k_receipt_events then reads every receipt a second time.  The lane
+//   * finds its value: the node's canonical leaf header (the low m bitmap bits, no links, m values) is compared as in
+//     k_dense_link_leaves, the values in front of its own are stepped over by their heads (receipt_end_fast);
+//   * type-checks its own value as check_value(VK_RECEIPT) does, keeping the events root, and writes the LeafRef;
+//   * resolves the events root to its block and the block's record (k_block_events) and writes the ReceiptRec and, when
+//     the table carries a filter, the match count — what k_receipt_events writes.
+// The node is validated by its values' lanes together: each checks its own value (and that receipt_end_fast, which the
+// lanes behind it step over it with, ends it where the reader does — so every lane's start is its value's start), the first
+// lane of a range that starts mid-node also those before it, the last lane of the node (or of a range that ends mid-node)
+// those behind it and the end of the block.  Anything else raises `anomaly`; every slot is written whatever happens (kNoBlock / RK_WALK): the kernels
+// queued behind read them before the host has seen the flag.
+__global__ __launch_bounds__(256) void k_dense_receipt_leaves(WitnessView w, const DenseNode* __restrict__ cur, const DenseRoots roots_arg,
+                                                              uint32_t root_i, uint32_t node_off0, uint32_t n_values,
+                                                              uint32_t* __restrict__ anomaly, LeafRef* __restrict__ leaves,
+                                                              DenseReceiptOut out) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_values) return;
+    const DenseRoot dr = roots_arg.r[root_i];
+    const uint64_t idx = dr.lo + t;
+    const uint32_t W = 1u << dr.bit_width;
+    const uint64_t pnode = idx >> dr.bit_width;
+    const uint32_t k = uint32_t(idx) & (W - 1u);
+    const DenseNode e = cur[node_off0 + uint32_t(pnode - dense_first(dr, 0))];
+    const uint64_t remaining = dr.count - pnode * W;
+    const uint32_t m = remaining < W ? uint32_t(remaining) : W;
+    LeafRef lr{kNoBlock, 0, 0, e.seq, idx};
+    ReceiptRec rr{RK_WALK, 0, 0, kNoBlock, 0};
+    uint32_t c = 0;
+    if (e.block != kNoBlock) {  // (else: reported where the link failed to resolve)
+        uint64_t h0, h1;
+        const uint32_t hdr = dense_header(W, m, true, h0, h1);
+        const uint8_t* node = w.arena + e.goff;
+        bool ok = hdr != 0 && hdr < e.rem && k < m && header_matches(node, hdr, h0, h1);
+        Rd rd;
+        rd.init(node, e.rem);
+        rd.pos = hdr;
+        const bool check_before = idx == dr.lo && k > 0;  // (values in front of the range have no lane of their own)
+        for (uint32_t i = 0; ok && i < k; ++i) {
+            const uint32_t end = check_before ? 0u : receipt_end_fast(node, rd.pos, e.rem);
+            if (end) {
+                rd.pos = end;
+            } else {
+                check_value(rd, VK_RECEIPT);
+                ok = rd.ok();
+            }
+        }
+        // this lane's value: check_receipt, the events root kept
+        const uint32_t start = rd.pos;
+        CidKey ev_root;
+        bool has_root = false;
+        if (ok) {
+            rd.expect_array(4);
+            if (rd.read_uint() > 0xffffffffULL) rd.fail();  // exit_code: u32
+            uint32_t o, l;
+            rd.read_bytes(o, l);
+            (void)rd.read_uint();
+            if (rd.at_null()) rd.read_null();
+            else has_root = rd.read_link_key(ev_root);
+            ok = rd.ok();
+        }
+        const uint32_t stop = rd.pos;
+        // the later lanes of the node step over this value with receipt_end_fast: where it says the value ends must be
+        // where the reader says, or the starts of the lanes behind would not be the values' starts
+        if (ok) {
+            const uint32_t fast = receipt_end_fast(node, start, e.rem);
+            ok = fast == 0u || fast == stop;
+        }
+        if (ok && (k + 1u == m || idx + 1u == dr.hi)) {  // the node's last lane: the values behind, nothing after them
+            for (uint32_t i = k + 1u; ok && i < m; ++i) {
+                check_value(rd, VK_RECEIPT);
+                ok = rd.ok();
+            }
+            if (ok && e.whole) {
+                rd.finish();
+                ok = rd.ok();
+            }
+        }
+        if (!ok) {
+            atomicOr(anomaly, 1u);
+        } else {
+            lr = LeafRef{e.block, uint32_t(e.goff - w.off[e.block]) + start, stop - start, e.seq, e.base + k};
+            rr.kind = RK_NO_EVENTS;
+            if (has_root) {
+                const uint32_t b = witness_find(w, ev_root);
+                rr.block = b;
+                if (b == kNoBlock) {
+                    rr.kind = IPCFP_ST_ERR_MISSING_BLOCK;
+                    atomicMin(out.err, (unsigned long long)pack_enum_error(1, t, rr.kind));
+                } else {
+                    const BlockRec br = out.brecs[b];
+                    if ((br.kind_matches & 0xffu) == RK_TABLE) {
+                        rr.kind = RK_TABLE;
+                        rr.first = br.first;
+                        rr.bitmap = br.bitmap;
+                        c = br.kind_matches >> 8;
+                    } else {
+                        rr.kind = RK_WALK;
+                        c = kWalkPending;
+                    }
+                }
+            }
+        }
+    }
+    leaves[dr.out_off + t] = lr;
+    out.rrecs[t] = rr;
+    if (out.counts) out.counts[t] = c;
+}
+
 __global__ void k_enum_check(const uint64_t* __restrict__ actual, uint64_t expected, uint32_t* __restrict__ mismatch) {
     if (threadIdx.x == 0 && blockIdx.x == 0 && *actual != expected) atomicOr(mismatch, 1u);
 }
@@ -832,7 +985,7 @@ void dense_plan(const std::vector<uint64_t>& root_info, uint32_t n_roots, int vk
 int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* frontier, const DensePlan& plan,
                       DenseNode* a, DenseNode* b, LeafRef* leaves_main, CidKey* keys_main, LeafRef* leaves_extra, uint32_t* anomaly_d,
                       hipStream_t leaves_stream, hipEvent_t fork_event, hipStream_t wide_stream, hipEvent_t wide_event,
-                      uint32_t narrow_max_wg, const DenseClear* clear) {
+                      uint32_t narrow_max_wg, const DenseClear* clear, const DenseReceiptOut* receipts) {
     const DenseNode* src = frontier;
     auto widen = [&]() -> hipError_t {  // the narrow stream's part ends here
         if (!wide_stream || ctx->stream == wide_stream) return hipSuccess;
@@ -905,9 +1058,30 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     // (every leaf node gets a lane here: those of key trees that have values leave at once, an EMPTY key tree's root is
     // validated here — no value lane looks at it)
     const uint32_t n_nodes = uint32_t(plan.n_level[0]);
+    if (receipts) {  // the receipts tree (the extra root, the last one) by its values; the nodes in front of it by nodes when
+                     // one of them is not a key tree with values (an empty message list's root)
+        const uint32_t ri = plan.n_use - 1;
+        const DenseRoot& rr = plan.roots.r[ri];
+        if (ri < n_key_roots || rr.out_sel != 2 || rr.vkind != VK_RECEIPT || !leaves_extra)
+            return set_error(ctx, IPCFP_E_INVALID, "dense walk: the receipt records want a receipts tree as the extra root");
+        const uint32_t r_nodes = uint32_t(dense_nodes(rr, 0)), before = n_nodes - r_nodes;
+        bool node_lanes = ri > n_key_roots;
+        for (uint32_t i = 0; i < n_key_roots; ++i) node_lanes = node_lanes || plan.roots.r[i].count == 0;
+        if (node_lanes)
+            hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(before, 256)), dim3(256), 0, ls, view, src, plan.roots, before, 0u,
+                               leaves_main, anomaly_d, nullptr);
+        const uint32_t n_values = uint32_t(rr.hi - rr.lo);
+        if (n_values)
+            hipLaunchKernelGGL(k_dense_receipt_leaves, dim3(div_up(n_values, 256)), dim3(256), 0, ls, view, src, plan.roots, ri,
+                               before, n_values, anomaly_d, leaves_extra, *receipts);
+        else  // (an empty receipts tree: its root node is validated the node way; there is no record to write)
+            hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(r_nodes, 256)), dim3(256), 0, ls, view, src, plan.roots, n_nodes, before,
+                               leaves_main, anomaly_d, leaves_extra);
+    } else {
+        hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(n_nodes, 256)), dim3(256), 0, ls, view, src, plan.roots, n_nodes, 0u,
+                           leaves_main, anomaly_d, leaves_extra);
+    }
     (void)key_nodes;
-    hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(n_nodes, 256)), dim3(256), 0, ls, view, src, plan.roots, n_nodes, 0u,
-                       leaves_main, anomaly_d, leaves_extra);
     if (clear && !n_key_values) {  // (no lane to take the passenger)
         if (clear->n_slots) IPCFP_HIP(ctx, hipMemsetAsync(clear->slots, 0xff, clear->n_slots * 8, ctx->stream));
         if (clear->n_words) IPCFP_HIP(ctx, hipMemsetAsync(clear->words, 0, clear->n_words * 4, ctx->stream));

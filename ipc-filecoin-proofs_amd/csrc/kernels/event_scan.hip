@@ -379,7 +379,6 @@ __device__ __forceinline__ bool rec_matches(const uint8_t* __restrict__ arena, c
 // One receipt per lane: events_root → block id → the block's record (k_block_events) → ReceiptRec and, when the table
 // was built with this scan's filter, the match count.  No block is parsed here except the receipt value itself; a
 // receipt whose block the table does not cover is marked for k_receipt_walk (counts[t] = kWalkPending).
-constexpr uint32_t kWalkPending = 0xffffffffu;
 
 __global__ __launch_bounds__(256) void k_receipt_events(WitnessView w, const LeafRef* __restrict__ receipts, uint32_t n,
                                                         int count_matches, const BlockRec* __restrict__ brecs,
@@ -728,6 +727,22 @@ int launch_receipt_events(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* r
         ProfileScope prof(ctx, IPCFP_K_EVENT_SCAN, stream);
         hipLaunchKernelGGL(k_receipt_events, dim3(div_up(n, 256)), dim3(256), 0, stream, w, receipts_d, n,
                            filter ? 1 : 0, brecs_d, rrecs_d, counts_d, err_d);
+        hipLaunchKernelGGL(k_receipt_walk, dim3(div_up(n, 256)), dim3(256), 0, stream, w, receipts_d, n, sp,
+                           filter ? 1 : 0, rrecs_d, counts_d, err_d);
+    }
+    IPCFP_HIP(ctx, hipGetLastError());
+    return IPCFP_OK;
+}
+
+int launch_receipt_walk(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n,
+                        const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor, const ReceiptRec* rrecs_d,
+                        uint32_t* counts_d, unsigned long long* err_d, hipStream_t stream) {
+    if (n == 0) return IPCFP_OK;
+    if (!stream) stream = ctx->stream;
+    ScanParams sp{};
+    if (filter) sp = ScanParams{*filter, actor, has_actor ? 1u : 0u, 0};
+    {
+        ProfileScope prof(ctx, IPCFP_K_EVENT_SCAN, stream);
         hipLaunchKernelGGL(k_receipt_walk, dim3(div_up(n, 256)), dim3(256), 0, stream, w, receipts_d, n, sp,
                            filter ? 1 : 0, rrecs_d, counts_d, err_d);
     }

@@ -59,14 +59,17 @@ constexpr uint64_t kEvIsLog = 1ull << 56, kEvCaseA = 1ull << 57;
 //     nothing but the arena — neither the CID index nor the receipts — so it runs on its own stream beside K1 and
 //     the receipts enumeration.  Outcome per block: a BlockRec.  A block that is not exactly the tabulated shape
 //     (or is no events AMT at all) is RK_WALK, which decides nothing.
-//   k_receipt_events (event_scan.hip)  one receipt per lane: events_root → block id → BlockRec → ReceiptRec.
-//     Receipts whose block is RK_WALK take the general walkers (k_receipt_walk), as before.
+//   k_receipt_events (event_scan.hip)  one receipt per lane: events_root → block id → BlockRec → ReceiptRec.  On the
+//     verify call's table route the receipts tree's leaf kernel writes the same records while it holds each receipt
+//     (k_dense_receipt_leaves, amt_enum.hip).  Receipts whose block is RK_WALK take the general walkers (k_receipt_walk).
 struct BlockRec {
     uint32_t kind_matches;  // bits 0..7: RK_TABLE | RK_WALK; bits 8..31: events matching the filter the table was built with
     uint32_t first;         // index of the first EventRec
     uint64_t bitmap;
 };
 static_assert(sizeof(BlockRec) == 16, "record layout");
+// counts[t] of a receipt whose events the table does not cover: k_receipt_walk counts it
+constexpr uint32_t kWalkPending = 0xffffffffu;
 
 // The EventRec pool is cut into kPoolParts equal partitions, each with its own fill counter on its own 128-byte line:
 // a wavefront reserves the records of its blocks with ONE atomic on the counter of partition (wavefront number mod

@@ -103,12 +103,14 @@ struct EventClaimPacked;
 int launch_ctx_headers(ipcfp_ctx* ctx, const WitnessView& w, TipsetCtxDev* ctxs_d, uint32_t n);
 struct CtxFinish;
 int launch_ctx_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a);
-int launch_exec_finish_fused(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* first_d, uint32_t* pos_d,
-                             uint64_t* tile_d, uint64_t* total_d, bool flags_ready = false);
+// the flags' prefix sum (decoupled look-back), positions (pos_d), inverse, total (total_d) and the context's tail in one
+// launch, the flags ready in a.first; ctl_d: exec_scan_ctl_words(a.raw_len) words that are zero when it is queued
+int launch_exec_scan_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* pos_d, uint64_t* total_d,
+                            unsigned long long* ctl_d);
+size_t exec_scan_ctl_words(uint32_t n);
 int launch_exec_insert(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, unsigned long long* slots_d, uint32_t mask);
 int launch_exec_insert_flags(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, unsigned long long* slots_d, uint32_t mask,
                              uint32_t* first_d);
-int launch_scan_tiles_u64(ipcfp_ctx* ctx, uint64_t* tile_sums_d, uint32_t ntiles, uint64_t* total_d);
 int launch_exec_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const uint64_t* total_d, const uint32_t* first_d,
                        const uint32_t* pos_d, uint32_t n, uint32_t* inv_d);
 // jobs_d: device array of {TipsetCtxDev* ctx, AmtRootSpec* roots (nullable), unsigned long long* err}
@@ -147,6 +149,10 @@ int launch_scan_pass2(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& receip
 // the event table (event_table.h), step 2: receipt → its block's record (filter nullable: no match counts); the
 // receipts the block table does not cover are walked
 struct BlockRec;
+// k_receipt_walk alone, behind records written elsewhere (k_dense_receipt_leaves)
+int launch_receipt_walk(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n,
+                        const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor, const ReceiptRec* rrecs_d,
+                        uint32_t* counts_d, unsigned long long* err_d, hipStream_t stream);
 int launch_receipt_events(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n,
                           const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor, const BlockRec* brecs_d,
                           ReceiptRec* rrecs_d, uint32_t* counts_d, unsigned long long* err_d, hipStream_t stream = nullptr);

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void k_exec_first(const CidKey* __restrict__ k
     first[i] = f;
 }
 
-__device__ __forceinline__ void ctx_finish_fields(TipsetCtxDev* __restrict__ c, const CtxFinish& a) {
+__device__ __forceinline__ void ctx_finish_fields(TipsetCtxDev* __restrict__ c, const CtxFinish& a, uint64_t total) {
     c->exec_status = IPCFP_ST_ERR_BAD_CLAIM;
     c->exec_slots = nullptr;
     c->exec_inv = nullptr;
@@ -147,7 +147,7 @@ __device__ __forceinline__ void ctx_finish_fields(TipsetCtxDev* __restrict__ c, 
     c->exec_keys = a.keys;
     c->exec_pos = a.pos;
     c->exec_inv = status == IPCFP_ST_TRUE ? a.inv : nullptr;
-    c->exec_len = status == IPCFP_ST_TRUE ? *a.total : 0;
+    c->exec_len = status == IPCFP_ST_TRUE ? total : 0;
     // the receipts AMT rode along with the message AMTs: a table lookup per claim
     c->receipt_leaves = a.receipt_leaves;
     c->n_receipt_leaves = a.n_receipt_leaves;
@@ -156,61 +156,88 @@ __device__ __forceinline__ void ctx_finish_fields(TipsetCtxDev* __restrict__ c, 
     c->event_recs = a.event_recs;
 }
 
-// stages 4-6 in two kernels instead of five (host/verify_fast.cpp): first-occurrence flags with their tile sums, then —
-// behind the scan of the 256-item tiles' sums (scan.hip k_scan_tiles_u64) — positions, the inverse permutation and the
-// context's tail (k_ctx_finish's part) in one pass
-__global__ __launch_bounds__(256) void k_exec_first_sums(const CidKey* __restrict__ keys, uint32_t n,
-                                                         const unsigned long long* __restrict__ slots, uint32_t mask,
-                                                         uint32_t* __restrict__ first, uint64_t* __restrict__ tile_sums) {
+// Stages 5-6 in ONE launch (host/verify_fast.cpp): the exclusive prefix sum of the first-occurrence flags as a single pass
+// with DECOUPLED LOOK-BACK (the pattern of k_scan_tail_fused: a ticket per workgroup, relaxed agent-scope atomics on state
+// words that carry the values themselves, no fence), positions and the inverse permutation, and — from the last tile in
+// ticket order, which holds the total — the context's tail.  (Was: the flags' tile sums, a one-workgroup scan of them and
+// an apply pass — three launches in a row on the way to the verify kernel.)
+//   ctl[0]: the ticket (low word); ctl[1 + tile] = flag << 32 | value, flag 1: the tile's aggregate, 2: the inclusive prefix
+//   up to it.  ALL ZERO on entry: the words ride behind the flags and are cleared with them (k_dense_link_leaves).
+constexpr uint32_t kExecTile = 1024;
+
+__global__ __launch_bounds__(256) void k_exec_scan_finish(const uint32_t* __restrict__ first, uint32_t n, uint32_t* __restrict__ pos,
+                                                          uint64_t* __restrict__ total_out, unsigned long long* __restrict__ ctl,
+                                                          TipsetCtxDev* __restrict__ c, CtxFinish a) {
     __shared__ uint64_t smem[17];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t f = 0;
-    if (i < n) {
-        const CidKey key = keys[i];
-        const uint64_t h = cid_hash64(key);
-        uint32_t s = uint32_t(h >> 32) & mask;
-        for (;;) {
-            const unsigned long long cur = slots[s];
-            if (cur == kEmptySlot64) break;  // cannot happen after stage 3; kept as a stop
-            if (uint32_t(cur >> 32) == uint32_t(h)) {
-                if (uint32_t(cur) == i) {  // the slot is this position's own: no key to read
-                    f = 1;
-                    break;
-                }
-                if (cid_equal(keys[uint32_t(cur)], key)) break;  // an earlier position holds the same CID
+    __shared__ uint32_t s_tile;
+    __shared__ uint64_t s_prefix;
+    const uint32_t n_tiles = (n + kExecTile - 1) / kExecTile;
+    unsigned long long* const state = ctl + 1;
+    if (threadIdx.x == 0) s_tile = atomicAdd(reinterpret_cast<unsigned int*>(ctl), 1u);
+    __syncthreads();
+    const uint32_t tile = s_tile;
+    const uint32_t base = tile * kExecTile + threadIdx.x * 4u;
+    uint32_t f[4];
+    uint64_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f[k] = base + k < n ? first[base + k] : 0u;
+        sum += f[k];
+    }
+    uint64_t tile_total;
+    const uint64_t ex = block_exclusive_scan(sum, smem, &tile_total);
+    if (threadIdx.x < 64) {  // publish, look back (wave 0)
+        const uint32_t lane = threadIdx.x;
+        if (lane == 0)
+            __hip_atomic_store(state + tile, ((tile == 0 ? 2ull : 1ull) << 32) | (tile_total & 0xffffffffull), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        uint64_t prefix = 0;
+        int32_t hi = int32_t(tile) - 1;  // the nearest predecessor not yet accounted for
+        while (hi >= 0) {
+            const int32_t j = hi - int32_t(lane);
+            unsigned long long v = 0;
+            bool ready = true;
+            if (j >= 0) {
+                v = __hip_atomic_load(state + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ready = ((v >> 32) & 3ull) != 0ull;
             }
-            s = (s + 1) & mask;
+            const uint64_t not_ready = __ballot(!ready);
+            const uint32_t usable = not_ready ? uint32_t(__builtin_ctzll(not_ready)) : 64u;  // lanes 0 .. usable-1
+            const uint64_t is_prefix = __ballot(ready && j >= 0 && ((v >> 32) & 3ull) == 2ull);
+            const uint64_t in_use = usable >= 64u ? ~0ull : ((1ull << usable) - 1ull);
+            const uint64_t pfx_in = is_prefix & in_use;
+            const uint32_t stop = pfx_in ? uint32_t(__builtin_ctzll(pfx_in)) : 64u;  // first inclusive prefix met
+            const uint32_t take = stop < 64u ? stop + 1u : usable;                   // lanes 0 .. take-1 contribute
+            uint64_t mine = (lane < take && j >= 0) ? (v & 0xffffffffull) : 0ull;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+            prefix += mine;
+            if (stop < 64u) break;
+            hi -= int32_t(take);
+            if (take == 0) __builtin_amdgcn_s_sleep(1);
         }
-        first[i] = f;
+        if (lane == 0) {
+            if (tile != 0)
+                __hip_atomic_store(state + tile, (2ull << 32) | ((prefix + tile_total) & 0xffffffffull), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            s_prefix = prefix;
+        }
     }
-    uint64_t total;
-    (void)block_exclusive_scan(uint64_t(f), smem, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// the tile sums of flags that are already there (k_exec_insert_flags)
-__global__ __launch_bounds__(256) void k_exec_flag_sums(const uint32_t* __restrict__ first, uint32_t n,
-                                                        uint64_t* __restrict__ tile_sums) {
-    __shared__ uint64_t smem[17];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t total;
-    (void)block_exclusive_scan(uint64_t(i < n ? first[i] : 0u), smem, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_exec_apply_finish(const uint32_t* __restrict__ first, uint32_t n,
-                                                           const uint64_t* __restrict__ tile_base, uint32_t* __restrict__ pos,
-                                                           TipsetCtxDev* __restrict__ c, CtxFinish a) {
-    __shared__ uint64_t smem[17];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t f = i < n ? first[i] : 0u;
-    uint64_t total;
-    const uint64_t ex = block_exclusive_scan(uint64_t(f), smem, &total) + tile_base[blockIdx.x];
-    if (i < n) {
-        pos[i] = uint32_t(ex);
-        if (f) a.inv[uint32_t(ex)] = i;
+    __syncthreads();
+    uint64_t o = s_prefix + ex;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t i = base + k;
+        if (i >= n) break;
+        pos[i] = uint32_t(o);
+        if (f[k]) a.inv[uint32_t(o)] = i;
+        o += f[k];
     }
-    if (i == 0) ctx_finish_fields(c, a);
+    if (tile == n_tiles - 1 && threadIdx.x == 0) {  // (what later launches read of these is ordered by the end of this one)
+        const uint64_t total = s_prefix + tile_total;
+        *total_out = total;
+        ctx_finish_fields(c, a, total);
+    }
 }
 
 // the distinct CIDs in execution order (ipcfp_exec_order)
@@ -331,21 +358,20 @@ __global__ __launch_bounds__(256) void k_exec_finish(TipsetCtxDev* __restrict__ 
 __global__ __launch_bounds__(256) void k_ctx_finish(TipsetCtxDev* __restrict__ c, CtxFinish a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < a.raw_len && a.first[i]) a.inv[a.pos[i]] = i;
-    if (i == 0) ctx_finish_fields(c, a);
+    if (i == 0) ctx_finish_fields(c, a, *a.total);
 }
 
-// first flags + tile sums, scan of the tile sums, positions + inverse + the context's tail.  tile_d: div_up(n, 256) + 1 words.
-int launch_exec_finish_fused(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* first_d, uint32_t* pos_d,
-                             uint64_t* tile_d, uint64_t* total_d, bool flags_ready) {
-    const uint32_t n = a.raw_len, ntiles = div_up(n ? n : 1, 256);
-    if (flags_ready) hipLaunchKernelGGL(k_exec_flag_sums, dim3(ntiles), dim3(256), 0, ctx->stream, first_d, n, tile_d);
-    else hipLaunchKernelGGL(k_exec_first_sums, dim3(ntiles), dim3(256), 0, ctx->stream, a.keys, n, a.slots, a.mask, first_d, tile_d);
-    int rc = launch_scan_tiles_u64(ctx, tile_d, ntiles, total_d);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_exec_apply_finish, dim3(ntiles), dim3(256), 0, ctx->stream, first_d, n, tile_d, pos_d, ctx_d, a);
+// ctl_d: exec_scan_ctl_words(a.raw_len) words, zero when this is queued
+int launch_exec_scan_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* pos_d, uint64_t* total_d,
+                            unsigned long long* ctl_d) {
+    const uint32_t n = a.raw_len;
+    if (n == 0) return set_error(ctx, IPCFP_E_INVALID, "exec scan: no messages");
+    hipLaunchKernelGGL(k_exec_scan_finish, dim3(div_up(n, kExecTile)), dim3(256), 0, ctx->stream, a.first, n, pos_d, total_d, ctl_d,
+                       ctx_d, a);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
+size_t exec_scan_ctl_words(uint32_t n) { return 1u + size_t(div_up(n, kExecTile)); }
 
 int launch_ctx_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a) {
     hipLaunchKernelGGL(k_ctx_finish, dim3(a.raw_len ? div_up(a.raw_len, 256) : 1), dim3(256), 0, ctx->stream, ctx_d, a);

@@ -19,10 +19,12 @@ KERNELS = [
     ("k_dense_top", "amt_walk", "lane_seq"),                # the narrow levels at the top, one workgroup
     ("k_dense_level", "amt_walk", "lane_seq"),              # one AMT node per lane, parsed front to back
     ("k_dense_link_leaves", "amt_walk", "lane_seq"),
+    ("k_dense_receipt_leaves", "amt_walk", "lane_seq"),     # the receipts' leaves AND their event records (verify table route)
     ("k_dense_leaves", "amt_walk", "lane_seq"),
     ("k_exec_insert", "exec_order", "rand16"),
-    ("k_exec_first_sums", "exec_order", "rand16"),
+    ("k_exec_first_sums", "exec_order", "rand16"),          # (earlier rounds' counters)
     ("k_exec_apply_finish", "exec_order", "rand16"),
+    ("k_exec_scan_finish", "exec_order", "stream"),         # flags read in order, positions written in order, inverse scattered
     ("k_block_events", "event_scan", "stream"),             # whole lines staged by the wavefront
     ("k_receipt_events", "event_scan", "rand64"),
     ("k_count_from_table", "event_scan", "stream"),

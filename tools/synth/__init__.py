@@ -38,6 +38,8 @@ class Params(C.Structure):
         ("storage_layout_mix", C.c_uint32),
         ("keep_full_state", C.c_uint32),
         ("n_actor_queries", C.c_uint64),
+        ("receipt_spelling", C.c_uint32),
+        ("receipt_hole", C.c_uint32),
     ]
 
 
@@ -45,7 +47,7 @@ DEFAULTS = dict(
     seed=SEED_BASE + 3, parent_epoch=2992953, n_parents=2, dup_permille=50, n_receipts=1000, max_events=4,
     no_events_permille=100, n_emitters=1024, emitter_base=1000, n_sigs=16, n_subnets=64, n_planted=10,
     filter_actor=1001, variety=0, events_bit_width=5, n_actors=0, actor_base=1000, n_contracts=0,
-    slots_per_contract=0, storage_layout_mix=0, keep_full_state=1, n_actor_queries=0,
+    slots_per_contract=0, storage_layout_mix=0, keep_full_state=1, n_actor_queries=0, receipt_spelling=0, receipt_hole=0,
 )
 
 _lib = None

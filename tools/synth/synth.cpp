@@ -257,6 +257,9 @@ struct synth_params {
     uint32_t storage_layout_mix;  // 1 ⇒ contracts cycle through layouts C,B1,B2,A1,A2,A3; 0 ⇒ all C
     uint32_t keep_full_state;  // 1 ⇒ every state-tree node is put in the witness; 0 ⇒ only query paths
     uint64_t n_actor_queries;  // PRNG-chosen present ids (+1% absent) whose paths are kept
+    uint32_t receipt_spelling; // 1 ⇒ receipts with long return data (up to 70 000 bytes) and non-minimal integer / length
+                               // heads, from a PRNG stream of their own (every other byte of the tipset is unchanged)
+    uint32_t receipt_hole;     // k > 0 ⇒ receipt k-1 is left out of the receipts AMT (a sparse leaf)
 };
 }
 
@@ -427,6 +430,7 @@ static Tipset* build(const synth_params& p) {
     std::vector<uint8_t> planted_flag(p.n_receipts, 0);
     for (uint64_t k = 0; k < p.n_planted && p.n_receipts; ++k) planted_flag[r.below(p.n_receipts)] = 1;
     std::vector<AmtVal> receipt_vals(p.n_receipts);
+    Rng rs(p.seed ^ 0x7265636569707473ULL);  // (receipt_spelling's own stream)
     const uint32_t ebw = p.events_bit_width ? p.events_bit_width : 5;
     for (uint64_t i = 0; i < p.n_receipts; ++i) {
         bool has_events = p.max_events > 0 && !(p.no_events_permille && r.below(1000) < p.no_events_permille);
@@ -462,13 +466,42 @@ static Tipset* build(const synth_params& p) {
         W w;
         uint8_t ret[8];
         r.fill(ret, 8);
+        const uint64_t exit_code = r.below(50) == 0 ? 1 + r.below(30) : 0;
+        const size_t ret_len = r.below(4) == 0 ? 8 : 0;
+        const uint64_t gas = r.below(1ull << 24);
         w.array(4);
-        w.uint(r.below(50) == 0 ? 1 + r.below(30) : 0);  // exit code
-        w.bytes(ret, r.below(4) == 0 ? 8 : 0);            // return data
-        w.uint(r.below(1ull << 24));                       // gas used
+        if (!p.receipt_spelling) {
+            w.uint(exit_code);
+            w.bytes(ret, ret_len);
+            w.uint(gas);
+        } else {
+            static const size_t kLens[] = {0, 8, 23, 24, 255, 256, 300, 65535, 65536, 70000};
+            const size_t n = kLens[rs.below(rs.below(400) == 0 ? 10 : 7)];  // (the big ones rarely)
+            Bytes data(n);
+            rs.fill(data.data(), n);
+            // a head of the value's minimal width or any wider one (the reader takes both)
+            auto any_head = [&](int major, uint64_t v) {
+                const int min_extra = v < 24 ? 0 : (v <= 0xff ? 1 : (v <= 0xffff ? 2 : (v <= 0xffffffffULL ? 4 : 8)));
+                static const int kExtra[] = {0, 1, 2, 4, 8};
+                int extra = min_extra;
+                if (rs.below(2) == 0) {
+                    const int x = kExtra[rs.below(5)];
+                    extra = x > min_extra ? x : min_extra;
+                }
+                const uint8_t m = uint8_t(major << 5);
+                if (extra == 0) { w.b.push_back(m | uint8_t(v)); return; }
+                w.b.push_back(m | uint8_t(extra == 1 ? 24 : (extra == 2 ? 25 : (extra == 4 ? 26 : 27))));
+                for (int k = extra - 1; k >= 0; --k) w.b.push_back(uint8_t(v >> (8 * k)));
+            };
+            any_head(0, rs.below(8) == 0 ? 0xffffffffULL - rs.below(3) : exit_code);        // exit code (u32)
+            any_head(2, n);                                                                     // return data
+            w.raw(data);
+            any_head(0, rs.below(4) == 0 ? rs.next() : (rs.below(2) ? gas : gas << 20));      // gas used
+        }
         if (has_events) w.link(events_root); else w.null();
         receipt_vals[i] = {i, std::move(w.b)};
     }
+    if (p.receipt_hole && p.receipt_hole <= receipt_vals.size()) receipt_vals.erase(receipt_vals.begin() + (p.receipt_hole - 1));
     {
         const uint64_t before = sink.payload;
         T->receipts_root = build_amt(sink, 0, 3, receipt_vals);
