@@ -200,7 +200,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     unsigned long long* const scan_ctl = reinterpret_cast<unsigned long long*>(ex.first.p + first_words);
     const DenseClear clear{ex.slots.p, size, ex.first.p, first_words + 2 * scan_ctl_words};
     // the receipts' event records, written by the receipts tree's leaf kernel (k_dense_receipt_leaves) on the aux stream,
-    // behind the block-order parse: allocated, and the error word set, before the walk is queued
+    // behind the block-order parse: allocated before the walk is queued; the walk's first interior kernel sets the error word
     std::unique_ptr<EventTableCached> table(new EventTableCached());
     table->lo = w->receipt_lo;
     table->hi = w->receipt_hi;
@@ -213,7 +213,6 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
         table->counts_filter = w->bt_filter;
         IPCFP_HIP(ctx, table->counts.alloc(n_rcpt));
     }
-    IPCFP_HIP(ctx, hipMemsetAsync(table->err_word.p, 0xff, 8, ctx->stream_aux));  // kNoEnumError
     const DenseReceiptOut recs{w->bt_blocks.p, table->receipts.p, table->has_counts ? table->counts.p : nullptr, table->err_word.p};
     prof.reset(new ProfileScope(ctx, IPCFP_K_AMT_WALK));
     // the receipt leaves (and their records) are consumed on the aux stream, the message keys on the main stream: the two

@@ -95,7 +95,7 @@ struct DenseReceiptOut {
     const BlockRec* brecs;     // k_block_events' records, ordered before the leaves on their stream
     ReceiptRec* rrecs;         // one per receipt of [lo, hi)
     uint32_t* counts;          // nullable: matches of the table's filter (kWalkPending where the table does not cover)
-    unsigned long long* err;   // the missing events blocks' error word (kNoEnumError on entry)
+    unsigned long long* err;   // the missing events blocks' error word (set to kNoEnumError by the walk's first interior launch)
 };
 void dense_plan(const std::vector<uint64_t>& root_info, uint32_t n_roots, int vkind, bool want_keys, uint64_t lo, uint64_t hi,
                 uint32_t has_extra, int extra_vkind, uint64_t extra_lo, uint64_t extra_hi, DensePlan& plan);

@@ -583,10 +583,13 @@ __device__ __forceinline__ void dense_level_one(const WitnessView& w, const Dens
     next[j] = c;
 }
 
+// `set_err` (non-null on the walk's first interior launch): the receipt records' error word, set to kNoEnumError here — ahead
+// of k_dense_receipt_leaves by stream order, without a fill of its own on the leaves' stream
 __global__ __launch_bounds__(256) void k_dense_level(WitnessView w, const DenseNode* __restrict__ cur, const DenseRoots roots_arg,
                                                      uint32_t level, uint32_t n_next, DenseNode* __restrict__ next,
-                                                     uint32_t* __restrict__ anomaly) {
+                                                     uint32_t* __restrict__ anomaly, unsigned long long* __restrict__ set_err) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (set_err && j == 0) *set_err = kNoEnumError;
     if (j < n_next) dense_level_one(w, cur, roots_arg.r, level, j, next, anomaly);
 }
 
@@ -601,7 +604,8 @@ struct DenseTopCounts {
 };
 __global__ __launch_bounds__(256) void k_dense_top(WitnessView w, const DenseNode* frontier, const DenseRoots roots_arg, uint32_t level_hi,
                                                    uint32_t n_levels, DenseTopCounts counts, DenseNode* a, DenseNode* b,
-                                                   uint32_t* __restrict__ anomaly) {
+                                                   uint32_t* __restrict__ anomaly, unsigned long long* __restrict__ set_err) {
+    if (set_err && threadIdx.x == 0) *set_err = kNoEnumError;  // (as k_dense_level)
     const DenseNode* src = frontier;
     for (uint32_t i = 0; i < n_levels; ++i) {
         const uint32_t n_next = counts.n[i];
@@ -733,22 +737,27 @@ __global__ __launch_bounds__(256) void k_dense_leaves(WitnessView w, const Dense
     }
 }
 
-// Where the receipt value at `s` of a node ends, from its heads alone — `84 | exit code | return data | gas used | null or
-// tag 42 + bytes` in two dependent fetches of plain loads (the value's start, then the one behind the return data) — or 0
-// when it is not spelled so (the caller then takes the reader).  It decides nothing: every value is type-checked by a lane
-// of its node, which refuses what the reader refuses.  Reads stay within 32 bytes of a position inside the block (blocks
-// sit on 128-byte lines, the arena has 256 bytes of tail slack).
-__device__ __forceinline__ uint32_t receipt_end_fast(const uint8_t* node, uint32_t s, uint32_t rem) {
+// The receipt value at `s` of a node — `84 | exit code | return data | gas used | null or the standard 43-byte link` —
+// settled from its heads: where it ends, or 0 when it is not spelled so (the caller then takes the reader).  What it
+// accepts is exactly what check_receipt accepts for those bytes, ending at the same place: an exit code of at most four
+// argument bytes (so a u32), a return-data length of at most four, the gas of any width, the events root null or the
+// standard link (read_link's fast form, `root` = true: the link ends the value).  Every byte it looks at lies in front of
+// the end it returns, and that end is ≤ rem — so bytes behind `rem` can only make it refuse.  `f8(i)`: the 8 bytes at node
+// byte i, little-endian; it is asked for at most 24 bytes behind a position < rem.  Two dependent fetches: the value's start,
+// then the bytes behind the return data.
+template <class F8>
+__device__ __forceinline__ uint32_t receipt_value_fast(const F8& f8, uint32_t s, uint32_t rem, bool& root) {
+    root = false;
     if (s >= rem) return 0;
-    const uint64_t a0 = load_u64_any(node + s), a1 = load_u64_any(node + s + 8), a2 = load_u64_any(node + s + 16);
-    auto ab = [&](uint32_t i) { return uint32_t((i < 8u ? a0 >> (8u * i) : (i < 16u ? a1 >> (8u * (i - 8u)) : a2 >> (8u * (i - 16u)))) & 0xffull); };
+    const uint64_t a0 = f8(s), a1 = f8(s + 8u);
+    auto ab = [&](uint32_t i) { return uint32_t((i < 8u ? a0 >> (8u * i) : a1 >> (8u * (i - 8u))) & 0xffull); };
     auto extra = [](uint32_t info) { return info < 24u ? 0u : (info == 24u ? 1u : (info == 25u ? 2u : (info == 26u ? 4u : (info == 27u ? 8u : 99u)))); };
     if (ab(0) != 0x84u) return 0;
     uint32_t b = ab(1);
     uint32_t x = extra(b & 31u);
-    if ((b >> 5) != 0u || x > 8u) return 0;  // exit code: an unsigned integer
-    uint32_t p = 2u + x;
-    b = ab(p);  // the return data: a byte string of at most 2^32 - 1 bytes
+    if ((b >> 5) != 0u || x > 4u) return 0;  // exit code: an unsigned integer of at most 4 argument bytes
+    const uint32_t p = 2u + x;
+    b = ab(p);  // the return data: a byte string
     x = extra(b & 31u);
     if ((b >> 5) != 2u || x > 4u) return 0;
     uint64_t len = b & 31u;
@@ -757,106 +766,165 @@ __device__ __forceinline__ uint32_t receipt_end_fast(const uint8_t* node, uint32
     else if (x == 4u) len = (uint64_t(ab(p + 1u)) << 24) | (ab(p + 2u) << 16) | (ab(p + 3u) << 8) | ab(p + 4u);
     const uint64_t g = uint64_t(s) + p + 1u + x + len;  // gas used
     if (g >= rem) return 0;
-    const uint64_t c0 = load_u64_any(node + g), c1 = load_u64_any(node + g + 8);
-    auto cb = [&](uint32_t i) { return uint32_t((i < 8u ? c0 >> (8u * i) : c1 >> (8u * (i - 8u))) & 0xffull); };
-    b = cb(0);
+    const uint64_t c0 = f8(uint32_t(g)), c1 = f8(uint32_t(g) + 8u), c2 = f8(uint32_t(g) + 16u);
+    auto cw = [&](uint32_t i) {  // the 8 bytes at byte i of the window c0 c1 c2 (zeros behind it)
+        const uint32_t sh = 8u * (i & 7u);
+        const uint64_t lo = i < 8u ? c0 : (i < 16u ? c1 : c2), hi = i < 8u ? c1 : (i < 16u ? c2 : 0ull);
+        return sh ? (lo >> sh) | (hi << (64u - sh)) : lo;
+    };
+    b = uint32_t(c0 & 0xffu);
     x = extra(b & 31u);
     if ((b >> 5) != 0u || x > 8u) return 0;
     const uint32_t q = 1u + x;
+    const uint64_t t0 = cw(q);
     uint64_t end;
-    if (cb(q) == 0xf6u) {
+    if ((t0 & 0xffu) == 0xf6u) {
         end = g + q + 1u;  // no events root
     } else {
-        if (cb(q) != 0xd8u || cb(q + 1u) != 0x2au) return 0;  // tag 42
-        b = cb(q + 2u);
-        if ((b >> 5) != 2u || (b & 31u) > 24u) return 0;
-        end = (b & 31u) < 24u ? g + q + 3u + (b & 31u) : g + q + 4u + cb(q + 3u);
+        if (t0 != 0xa071010027582ad8ull || (cw(q + 8u) & 0xffffffull) != 0x2002e4ull) return 0;
+        end = g + q + 43u;
+        root = true;
     }
     return end <= rem ? uint32_t(end) : 0u;
 }
 
-// Leaf level of the RECEIPTS tree on the verify call's table route (host/verify_fast.cpp): one lane per receipt VALUE, where
-// k_dense_leaves takes one lane per leaf node (its values decoded one after the other, 3.9 k wavefronts for 1 M receipts)
-// and k_receipt_events then reads every receipt a second time.  The lane
-//   * finds its value: the node's canonical leaf header (the low m bitmap bits, no links, m values) is compared as in
-//     k_dense_link_leaves, the values in front of its own are stepped over by their heads (receipt_end_fast);
-//   * type-checks its own value as check_value(VK_RECEIPT) does, keeping the events root, and writes the LeafRef;
-//   * resolves the events root to its block and the block's record (k_block_events) and writes the ReceiptRec and, when
-//     the table carries a filter, the match count — what k_receipt_events writes.
-// The node is validated by its values' lanes together: each checks its own value (and that receipt_end_fast, which the
-// lanes behind it step over it with, ends it where the reader does — so every lane's start is its value's start), the first
-// lane of a range that starts mid-node also those before it, the last lane of the node (or of a range that ends mid-node)
-// those behind it and the end of the block.  Anything else raises `anomaly`; every slot is written whatever happens (kNoBlock / RK_WALK): the kernels
-// queued behind read them before the host has seen the flag.
-__global__ __launch_bounds__(256) void k_dense_receipt_leaves(WitnessView w, const DenseNode* __restrict__ cur, const DenseRoots roots_arg,
-                                                              uint32_t root_i, uint32_t node_off0, uint32_t n_values,
-                                                              uint32_t* __restrict__ anomaly, LeafRef* __restrict__ leaves,
-                                                              DenseReceiptOut out) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_values) return;
-    const DenseRoot dr = roots_arg.r[root_i];
-    const uint64_t idx = dr.lo + t;
-    const uint32_t W = 1u << dr.bit_width;
-    const uint64_t pnode = idx >> dr.bit_width;
-    const uint32_t k = uint32_t(idx) & (W - 1u);
-    const DenseNode e = cur[node_off0 + uint32_t(pnode - dense_first(dr, 0))];
+// Leaf level of the RECEIPTS tree on the verify call's table route (host/verify_fast.cpp): a GROUP of G = min(W, 64) lanes
+// per leaf node, lane k for value k — where k_dense_leaves takes one lane per leaf node (its values decoded one after the
+// other) and k_receipt_events then reads every receipt a second time.  The group
+//   * stages the node in LDS (up to kReceiptStageBytes per value, less 16): one 16-byte load per lane and step, the group's
+//     loads side by side over the node;
+//   * compares the canonical leaf header (the low m bitmap bits, no links, m values) and finds every value's start in ONE
+//     pass over the stage — each lane makes the same pass, so the starts need no sharing: receipt_value_fast validates a
+//     value from its heads, the reader on global memory takes what it refuses (check_value(VK_RECEIPT)), so every value of
+//     the node is type-checked, those in front of or behind the range included, and behind the last one the end of the block;
+//   * then resolves, every lane at once, the events root of its value to the block's record (k_block_events) and writes
+//     the LeafRef, the ReceiptRec and, when the table carries a filter, the match count — what k_receipt_events wrote.
+// A node larger than its stage is walked the same way on global memory.  Anything else raises `anomaly`; every slot is
+// written whatever happens (kNoBlock / RK_WALK): the kernels queued behind read them before the host has seen the flag.
+constexpr uint32_t kReceiptStageBytes = 64;  // LDS per lane: a group stages nodes of up to G · 64 - 16 bytes
+constexpr uint32_t kReceiptStageSlack = 6;   // words behind a group's stage: what a fetch near the node's end reads beyond it
+__host__ __device__ inline uint32_t receipt_leaf_group(uint32_t bit_width) { return bit_width >= 6u ? 64u : (1u << bit_width); }
+__host__ __device__ inline uint32_t receipt_stage_words(uint32_t G) { return G * (kReceiptStageBytes / 8u) + kReceiptStageSlack; }
+
+// (the receipts root travels alone: DenseRoots indexed at run time would sit in scratch)
+__global__ __launch_bounds__(256) void k_dense_receipt_leaves(WitnessView w, const DenseNode* __restrict__ cur, const DenseRoot dr,
+                                                              uint32_t node_off0, uint32_t n_nodes, uint32_t* __restrict__ anomaly,
+                                                              LeafRef* __restrict__ leaves, DenseReceiptOut out) {
+    extern __shared__ uint64_t receipt_stage[];
+    const uint32_t W = 1u << dr.bit_width, G = receipt_leaf_group(dr.bit_width);  // (G divides the workgroup: groups sit in one wavefront)
+    const uint32_t gid = (blockIdx.x * blockDim.x + threadIdx.x) / G, j = threadIdx.x & (G - 1u);
+    if (gid >= n_nodes) return;  // (whole groups)
+    uint64_t* const st = receipt_stage + (threadIdx.x / G) * receipt_stage_words(G);
+    const uint64_t pnode = dense_first(dr, 0) + gid;
+    const DenseNode e = cur[node_off0 + gid];
     const uint64_t remaining = dr.count - pnode * W;
     const uint32_t m = remaining < W ? uint32_t(remaining) : W;
-    LeafRef lr{kNoBlock, 0, 0, e.seq, idx};
-    ReceiptRec rr{RK_WALK, 0, 0, kNoBlock, 0};
-    uint32_t c = 0;
-    if (e.block != kNoBlock) {  // (else: reported where the link failed to resolve)
-        uint64_t h0, h1;
-        const uint32_t hdr = dense_header(W, m, true, h0, h1);
-        const uint8_t* node = w.arena + e.goff;
-        bool ok = hdr != 0 && hdr < e.rem && k < m && header_matches(node, hdr, h0, h1);
+    uint64_t h0, h1;
+    const uint32_t hdr = dense_header(W, m, true, h0, h1);  // (0 for W > 64: no lane has a value of its own then)
+    const bool live = e.block != kNoBlock;                  // (else: reported where the link failed to resolve)
+    bool ok = live && hdr != 0 && hdr < e.rem;
+    const uint8_t* node = w.arena + e.goff;
+    const uint32_t sh = uint32_t(e.goff & 15u);
+    const bool staged = ok && e.rem <= G * kReceiptStageBytes - 16u;  // (the same for the whole group)
+    if (staged) {  // chunks [0, n_ch) of the 16-byte-aligned lines under the node (blocks sit on 128-byte lines)
+        const ulonglong2* src = reinterpret_cast<const ulonglong2*>(node - sh);
+        const uint32_t n_ch = (sh + e.rem + 15u) / 16u;  // ≤ G · kReceiptStageBytes / 16
+        ulonglong2 v[kReceiptStageBytes / 16u];
+#pragma unroll
+        for (uint32_t i = 0; i < kReceiptStageBytes / 16u; ++i)
+            if (j + G * i < n_ch) v[i] = src[j + G * i];
+#pragma unroll
+        for (uint32_t i = 0; i < kReceiptStageBytes / 16u; ++i)
+            if (j + G * i < n_ch) {
+                st[2u * (j + G * i)] = v[i].x;
+                st[2u * (j + G * i) + 1u] = v[i].y;
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    const auto f8_stage = [&](uint32_t i) __attribute__((always_inline)) {
+        const uint32_t q = sh + i, r = 8u * (q & 7u);
+        const uint64_t lo = st[q >> 3], hi = st[(q >> 3) + 1u];
+        return r ? (lo >> r) | (hi << (64u - r)) : lo;
+    };
+    const auto f8_global = [&](uint32_t i) __attribute__((always_inline)) { return load_u64_any(node + i); };
+    // the pass over the node: header, every value, the end; this lane keeps where its own value k = j lies
+    uint32_t start = 0, stop = 0;
+    bool mine_fast = false, mine_root = false;
+    const auto pass = [&](const auto& f8) __attribute__((always_inline)) {
+        const uint64_t g0 = f8(0u), g1 = f8(8u);
+        const uint64_t m0 = hdr >= 8 ? ~0ull : ((1ull << (8u * hdr)) - 1ull);
+        const uint64_t m1 = hdr <= 8 ? 0ull : (hdr >= 16 ? ~0ull : ((1ull << (8u * (hdr - 8u))) - 1ull));
+        ok = ((g0 ^ h0) & m0) == 0 && ((g1 ^ h1) & m1) == 0;  // header_matches
         Rd rd;
         rd.init(node, e.rem);
-        rd.pos = hdr;
-        const bool check_before = idx == dr.lo && k > 0;  // (values in front of the range have no lane of their own)
-        for (uint32_t i = 0; ok && i < k; ++i) {
-            const uint32_t end = check_before ? 0u : receipt_end_fast(node, rd.pos, e.rem);
-            if (end) {
-                rd.pos = end;
-            } else {
+        uint32_t pos = hdr;
+        for (uint32_t i = 0; ok && i < m; ++i) {
+            bool root;
+            uint32_t end = receipt_value_fast(f8, pos, e.rem, root);
+            const bool fast = end != 0u;
+            if (!fast) {  // a spelling the heads do not settle: the reader decides
+                rd.pos = pos;
                 check_value(rd, VK_RECEIPT);
                 ok = rd.ok();
+                end = rd.pos;
             }
+            if (i == j) {
+                start = pos;
+                stop = end;
+                mine_fast = fast;
+                mine_root = root;
+            }
+            pos = end;
         }
-        // this lane's value: check_receipt, the events root kept
-        const uint32_t start = rd.pos;
-        CidKey ev_root;
-        bool has_root = false;
-        if (ok) {
+        if (ok && e.whole) ok = pos == e.rem;  // nothing after the last value
+    };
+    if (staged) pass(f8_stage);
+    else if (ok) pass(f8_global);
+    if (live && !ok) atomicOr(anomaly, 1u);
+    // this lane's value: the events root, from the stage when the heads settled the value, else from the reader
+    CidKey ev_root;
+    bool has_root = false;
+    if (ok && j < m) {
+        if (mine_fast) {
+            has_root = mine_root;
+            if (has_root) {  // std_link_key of the link that ends the value
+#pragma unroll
+                for (int q = 0; q < 5; ++q) ev_root.w[q] = staged ? f8_stage(stop - 38u + 8u * q) : f8_global(stop - 38u + 8u * q);
+                ev_root.w[4] &= (1ull << 48) - 1ull;
+            }
+        } else {
+            Rd rd;
+            rd.init(node, e.rem);
+            rd.pos = start;
             rd.expect_array(4);
             if (rd.read_uint() > 0xffffffffULL) rd.fail();  // exit_code: u32
             uint32_t o, l;
             rd.read_bytes(o, l);
             (void)rd.read_uint();
-            if (rd.at_null()) rd.read_null();
-            else has_root = rd.read_link_key(ev_root);
-            ok = rd.ok();
-        }
-        const uint32_t stop = rd.pos;
-        // the later lanes of the node step over this value with receipt_end_fast: where it says the value ends must be
-        // where the reader says, or the starts of the lanes behind would not be the values' starts
-        if (ok) {
-            const uint32_t fast = receipt_end_fast(node, start, e.rem);
-            ok = fast == 0u || fast == stop;
-        }
-        if (ok && (k + 1u == m || idx + 1u == dr.hi)) {  // the node's last lane: the values behind, nothing after them
-            for (uint32_t i = k + 1u; ok && i < m; ++i) {
-                check_value(rd, VK_RECEIPT);
-                ok = rd.ok();
+            if (rd.at_null()) {
+                rd.read_null();
+            } else {  // (a CID longer than a witness key: the general walk folds it — no Blake2b in this kernel)
+                uint32_t co, cl;
+                rd.read_link(co, cl);
+                if (cl > 40u) rd.fail();
+                has_root = rd.ok();
+                if (has_root) ev_root = rd.key_at(co, cl);
             }
-            if (ok && e.whole) {
-                rd.finish();
-                ok = rd.ok();
-            }
+            ok = rd.ok() && rd.pos == stop;  // (the pass's reader took this value already: it ends where the pass said)
+            if (!ok) atomicOr(anomaly, 1u);
         }
-        if (!ok) {
-            atomicOr(anomaly, 1u);
-        } else {
+    }
+    // every slot of the range this lane answers for (one, value j, unless W > 64: then the node is an anomaly)
+    for (uint32_t k = j; k < m; k += G) {
+        const uint64_t idx = pnode * W + k;
+        if (idx < dr.lo || idx >= dr.hi) continue;
+        const uint32_t t = uint32_t(idx - dr.lo);
+        LeafRef lr{kNoBlock, 0, 0, e.seq, idx};
+        ReceiptRec rr{RK_WALK, 0, 0, kNoBlock, 0};
+        uint32_t c = 0;
+        if (ok && k == j) {
             lr = LeafRef{e.block, uint32_t(e.goff - w.off[e.block]) + start, stop - start, e.seq, e.base + k};
             rr.kind = RK_NO_EVENTS;
             if (has_root) {
@@ -879,10 +947,10 @@ __global__ __launch_bounds__(256) void k_dense_receipt_leaves(WitnessView w, con
                 }
             }
         }
+        leaves[dr.out_off + t] = lr;
+        out.rrecs[t] = rr;
+        if (out.counts) out.counts[t] = c;
     }
-    leaves[dr.out_off + t] = lr;
-    out.rrecs[t] = rr;
-    if (out.counts) out.counts[t] = c;
 }
 
 __global__ void k_enum_check(const uint64_t* __restrict__ actual, uint64_t expected, uint32_t* __restrict__ mismatch) {
@@ -999,6 +1067,7 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     // latency of its three dependent loads under their memory traffic, not the dispatch; a barrier adds an L2
     // write-back and an L1 invalidate per level on top.  profiles/r03_experiments.md)
     uint32_t level_from = plan.max_height;
+    unsigned long long* set_err = receipts ? receipts->err : nullptr;  // (taken by the first interior launch)
     {   // the narrow levels at the top: one launch (k_dense_top).  IPCFP_DENSE_TOP = the widest level it takes (0: none)
         static const uint32_t top_max = [] {
             const char* e = std::getenv("IPCFP_DENSE_TOP");
@@ -1011,7 +1080,9 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
             ++n_top;
         }
         if (n_top >= 2) {  // (one level alone is k_dense_level's)
-            hipLaunchKernelGGL(k_dense_top, dim3(1), dim3(256), 0, ctx->stream, view, src, plan.roots, level_from, n_top, counts, a, b, anomaly_d);
+            hipLaunchKernelGGL(k_dense_top, dim3(1), dim3(256), 0, ctx->stream, view, src, plan.roots, level_from, n_top, counts, a, b, anomaly_d,
+                               set_err);
+            set_err = nullptr;
             // the last level written: a for an odd number of levels, b for an even one — and the next writes the other
             if (n_top & 1u) {
                 src = a;
@@ -1027,7 +1098,9 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     for (uint32_t level = level_from; level >= 1; --level) {
         const uint32_t nn = uint32_t(plan.n_level[level - 1]);
         if (div_up(nn, 256) > narrow_max_wg) IPCFP_HIP(ctx, widen());
-        hipLaunchKernelGGL(k_dense_level, dim3(div_up(nn, 256)), dim3(256), 0, ctx->stream, view, src, plan.roots, level, nn, a, anomaly_d);
+        hipLaunchKernelGGL(k_dense_level, dim3(div_up(nn, 256)), dim3(256), 0, ctx->stream, view, src, plan.roots, level, nn, a, anomaly_d,
+                           set_err);
+        set_err = nullptr;
         src = a;
         DenseNode* t = a;
         a = b;
@@ -1049,6 +1122,7 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     // leaves feed k_receipt_events on the aux stream) forks here: k_dense_leaves goes to `leaves_stream`, ordered behind
     // the last interior level by `fork_event`, and runs beside k_dense_link_leaves instead of after it.
     IPCFP_HIP(ctx, widen());
+    if (set_err) IPCFP_HIP(ctx, hipMemsetAsync(set_err, 0xff, sizeof *set_err, ctx->stream));  // (no interior level: the roots are leaves)
     hipStream_t ls = ctx->stream;
     if (leaves_stream && leaves_stream != ctx->stream && fork_event) {
         IPCFP_HIP(ctx, hipEventRecord(fork_event, ctx->stream));
@@ -1070,11 +1144,12 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
         if (node_lanes)
             hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(before, 256)), dim3(256), 0, ls, view, src, plan.roots, before, 0u,
                                leaves_main, anomaly_d, nullptr);
-        const uint32_t n_values = uint32_t(rr.hi - rr.lo);
-        if (n_values)
-            hipLaunchKernelGGL(k_dense_receipt_leaves, dim3(div_up(n_values, 256)), dim3(256), 0, ls, view, src, plan.roots, ri,
-                               before, n_values, anomaly_d, leaves_extra, *receipts);
-        else  // (an empty receipts tree: its root node is validated the node way; there is no record to write)
+        if (rr.hi > rr.lo) {  // a group of lanes per leaf node, its stage in LDS
+            const uint32_t G = receipt_leaf_group(rr.bit_width);
+            hipLaunchKernelGGL(k_dense_receipt_leaves, dim3(div_up(uint64_t(r_nodes) * G, 256)), dim3(256),
+                               (256u / G) * receipt_stage_words(G) * sizeof(uint64_t), ls, view, src, rr, before, r_nodes, anomaly_d,
+                               leaves_extra, *receipts);
+        } else  // (an empty receipts tree: its root node is validated the node way; there is no record to write)
             hipLaunchKernelGGL(k_dense_leaves, dim3(div_up(r_nodes, 256)), dim3(256), 0, ls, view, src, plan.roots, n_nodes, before,
                                leaves_main, anomaly_d, leaves_extra);
     } else {
