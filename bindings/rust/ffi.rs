@@ -39,6 +39,7 @@ use crate::proofs::trust::TrustPolicy;
 #[repr(C)] pub struct ipcfp_witness_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_bundle_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_packed_events_t { _p: [u8; 0] }
+#[repr(C)] pub struct ipcfp_storage_columns_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_comm_t { _p: [u8; 0] }
 
 // ---- PODs of include/ipcfp.h --------------------------------------------------------------------------------------
@@ -445,6 +446,26 @@ impl Witness<'_> {
         let mut st = vec![0u8; raw.len()];
         let rc = unsafe { ipcfp_verify_storage_proofs(self.eng.ctx, self.raw(), raw.as_ptr(), raw.len() as u64, trust, st.as_mut_ptr()) };
         if rc != 0 { return Err(self.eng.err("ipcfp_verify_storage_proofs", rc)); }
+        statuses_to_result(&st)
+    }
+
+    /// The same through the run-compressed column form (include/ipcfp.h "storage claims in run-compressed, column form"):
+    /// the strings are lowered once on the host (parallel), consecutive proofs of one contract collapse into a run
+    /// record, and 65 bytes per claim + 192 per run cross PCIe instead of 248 per claim.  Same verdicts.
+    pub fn verify_storage_proofs_columns(&self, proofs: &[StorageProof], trust: &ipcfp_trust_policy_t) -> Result<Vec<bool>> {
+        let keep: Vec<_> = proofs.iter().map(CStorageProof::new).collect();
+        let raw: Vec<ipcfp_storage_proof_t> = keep.iter().map(|k| k.raw()).collect();
+        let mut packed: Vec<ipcfp_storage_claim_t> = Vec::with_capacity(raw.len());
+        let rc = unsafe { ipcfp_pack_storage_proofs(raw.as_ptr(), raw.len() as u64, packed.as_mut_ptr()) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_pack_storage_proofs", rc)); }
+        unsafe { packed.set_len(raw.len()) };
+        let mut cols: *mut ipcfp_storage_columns_t = std::ptr::null_mut();
+        let rc = unsafe { ipcfp_compact_storage_claims(packed.as_ptr(), packed.len() as u64, &mut cols) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_compact_storage_claims", rc)); }
+        let mut st = vec![0u8; raw.len()];
+        let rc = unsafe { ipcfp_verify_storage_columns(self.eng.ctx, self.raw(), cols, trust, st.as_mut_ptr()) };
+        unsafe { ipcfp_storage_columns_destroy(cols) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_verify_storage_columns", rc)); }
         statuses_to_result(&st)
     }
 

@@ -702,6 +702,75 @@ int ipcfp_pack_storage_proofs(const ipcfp_storage_proof_t* proofs, uint64_t n, i
 int ipcfp_verify_storage_claims_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const void* claims_d, uint64_t n,
                                        const ipcfp_trust_policy_t* trust, void* status_d);
 
+/* The same over packed claims in HOST memory (claims: n structs, status: n bytes, both host): upload, verify, status
+ * bytes back — the PCIe-inclusive form, the sibling of ipcfp_verify_event_claims.  The upload runs beside the node
+ * table of the witness, which needs no claim.                                                                   */
+int ipcfp_verify_storage_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipcfp_storage_claim_t* claims, uint64_t n,
+                                const ipcfp_trust_policy_t* trust, ipcfp_status_t* status);
+
+/* ---- storage claims in run-compressed, column form ----------------------------------------------------------------
+ * The proofs of a bundle are `storage_proofs: Vec<StorageProof>` (src/proofs/common/bundle.rs:36-45, fields:
+ * src/proofs/storage/bundle.rs:5-14) and the reference walks them in order (src/proofs/verifier.rs:19-28).  176 of an
+ * ipcfp_storage_claim_t's 248 bytes — child CID, state root, actor-state CID, storage root, actor id, epoch — say the
+ * same thing for every claim of one contract.  The transport form says them once per RUN:
+ *
+ *   run table   n_runs records of IPCFP_SRUN_BYTES, little-endian, at the byte offsets below.  A run is a stretch of
+ *               consecutive claims that agree on child_epoch, actor_id, the four CID slots and the four CID flag bits
+ *               (IPCFP_SCLAIM_CHILD_PARSED, _STATE_ROOT_CANON, _ACTOR_STATE_CANON, _STORAGE_ROOT_CANON).  The runs tile
+ *               [0, n) in order: run 0 starts at claim 0, no run is empty, every run starts where its predecessor ends,
+ *               the last ends at n.  Runs need not be maximal (neighbours with equal keys give the same verdicts).
+ *   columns     in claim order: slot u8[n][32], value u8[n][32], cflags u8[n] holding only
+ *               IPCFP_SCLAIM_SLOT_PARSED | IPCFP_SCLAIM_VALUE_MATCHABLE at their bit values.
+ *
+ * 65 bytes per claim + 192 per run: 10 000 contracts × 257 claims are 168.97 MB against 637.36 MB (0.265).
+ * Device arrays handed to the *_device entry points: the run table, slot and value columns on 16-byte boundaries.
+ * The form is untrusted input: a run table that does not tile [0, n) makes a verify / expand call return
+ * IPCFP_E_INVALID with no verdicts (checked on the device, every read bounded by n_runs and n); unknown bits in a run's
+ * flags, a non-zero reserved word, or unknown bits in a claim's cflags byte give the claims concerned
+ * IPCFP_ST_ERR_BAD_CLAIM.                                                                                          */
+#define IPCFP_SRUN_BYTES 192u
+#define IPCFP_SRUN_OFF_CHILD_EPOCH 0u    /* i64                                               */
+#define IPCFP_SRUN_OFF_ACTOR_ID 8u       /* u64                                               */
+#define IPCFP_SRUN_OFF_CHILD 16u         /* u8[IPCFP_CID_SLOT]                                */
+#define IPCFP_SRUN_OFF_STATE_ROOT 56u    /* u8[IPCFP_CID_SLOT]                                */
+#define IPCFP_SRUN_OFF_ACTOR_STATE 96u   /* u8[IPCFP_CID_SLOT]                                */
+#define IPCFP_SRUN_OFF_STORAGE_ROOT 136u /* u8[IPCFP_CID_SLOT]                                */
+#define IPCFP_SRUN_OFF_FIRST_CLAIM 176u  /* u32: index of the run's first claim               */
+#define IPCFP_SRUN_OFF_N_CLAIMS 180u     /* u32: > 0                                          */
+#define IPCFP_SRUN_OFF_FLAGS 184u        /* u32: the four CID bits of IPCFP_SCLAIM_*          */
+#define IPCFP_SRUN_OFF_RESERVED 188u     /* u32: 0                                            */
+#define IPCFP_SRUN_FLAG_MASK 15u
+#define IPCFP_SCOL_FLAG_MASK 48u         /* IPCFP_SCLAIM_SLOT_PARSED | IPCFP_SCLAIM_VALUE_MATCHABLE */
+
+/* Host only (no context, no device; parallel over claims): n plain claims → a handle that owns the run table (maximal
+ * runs) and the three columns.  IPCFP_E_UNSUPPORTED for what could not come back byte for byte: reserved != 0, flag
+ * bits >= 64, n >= 2^32 - 1.  n == 0 gives an empty, valid handle.                                                  */
+typedef struct ipcfp_storage_columns ipcfp_storage_columns_t;
+int ipcfp_compact_storage_claims(const ipcfp_storage_claim_t* claims, uint64_t n, ipcfp_storage_columns_t** out);
+void ipcfp_storage_columns_destroy(ipcfp_storage_columns_t* c);
+uint64_t ipcfp_storage_columns_count(const ipcfp_storage_columns_t* c);                       /* n */
+const uint8_t* ipcfp_storage_columns_runs(const ipcfp_storage_columns_t* c, uint32_t* n_runs); /* n_runs × IPCFP_SRUN_BYTES */
+const uint8_t* ipcfp_storage_columns_slots(const ipcfp_storage_columns_t* c);                 /* n × 32 */
+const uint8_t* ipcfp_storage_columns_values(const ipcfp_storage_columns_t* c);                /* n × 32 */
+const uint8_t* ipcfp_storage_columns_cflags(const ipcfp_storage_columns_t* c);                /* n */
+uint64_t ipcfp_storage_columns_bytes(const ipcfp_storage_columns_t* c);  /* 65 n + 192 n_runs: what crosses PCIe */
+/* columns → ipcfp_storage_claim_t[n] on the host (claims_out: room for n) */
+int ipcfp_expand_storage_claims(const ipcfp_storage_columns_t* c, ipcfp_storage_claim_t* claims_out);
+
+/* verify_storage_proof over the column form resident in HBM (status_d: n bytes): no run discovery, every run's key read
+ * from its record, slot and value read as contiguous columns.  Verdicts are those of ipcfp_verify_storage_claims_device
+ * over the expanded claims.                                                                                          */
+int ipcfp_verify_storage_columns_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const void* runs_d, uint32_t n_runs,
+                                        const void* slot_d, const void* value_d, const void* cflags_d, uint64_t n,
+                                        const ipcfp_trust_policy_t* trust, void* status_d);
+/* The same from a handle in HOST memory: upload (beside the node table), verify, status bytes back in host memory. */
+int ipcfp_verify_storage_columns(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipcfp_storage_columns_t* cols,
+                                 const ipcfp_trust_policy_t* trust, ipcfp_status_t* status);
+/* columns → ipcfp_storage_claim_t[n] on the device (claims_out_d: 16-byte aligned, room for n), byte for byte what
+ * ipcfp_expand_storage_claims gives.                                                                                */
+int ipcfp_expand_storage_claims_device(ipcfp_ctx_t* ctx, const void* runs_d, uint32_t n_runs, const void* slot_d,
+                                       const void* value_d, const void* cflags_d, uint64_t n, void* claims_out_d);
+
 /* Rebuild the CID → block index of an existing witness in place (K4), e.g. once per verification
  * pass when the index build is to be charged to that pass.  No allocation.                    */
 int ipcfp_witness_rebuild_index(ipcfp_ctx_t* ctx, ipcfp_witness_t* w);

@@ -50,6 +50,9 @@ __all__ = [
     "GROUP_DTYPE",
     "pack_storage_claims",
     "SCLAIM_DTYPE",
+    "compact_storage_claims",
+    "expand_storage_claims",
+    "StorageColumns",
     "cid_from_string",
     "cid_to_string",
     "pack_cids",
@@ -323,6 +326,19 @@ def load_library() -> C.CDLL:
         "ipcfp_scan_events_device": (i32, [vp, vp, vp, vp, i32, u64, vp, vp, u64, C.POINTER(u64), vp, u64, C.POINTER(u64), vp]),
         "ipcfp_witness_last_scan_phase": (i32, [vp]),
         "ipcfp_verify_storage_claims_device": (i32, [vp, vp, vp, u64, vp, vp]),
+        "ipcfp_verify_storage_claims": (i32, [vp, vp, vp, u64, vp, vp]),
+        "ipcfp_compact_storage_claims": (i32, [vp, u64, C.POINTER(vp)]),
+        "ipcfp_storage_columns_destroy": (None, [vp]),
+        "ipcfp_storage_columns_count": (u64, [vp]),
+        "ipcfp_storage_columns_runs": (vp, [vp, C.POINTER(C.c_uint32)]),
+        "ipcfp_storage_columns_slots": (vp, [vp]),
+        "ipcfp_storage_columns_values": (vp, [vp]),
+        "ipcfp_storage_columns_cflags": (vp, [vp]),
+        "ipcfp_storage_columns_bytes": (u64, [vp]),
+        "ipcfp_expand_storage_claims": (i32, [vp, vp]),
+        "ipcfp_verify_storage_columns_device": (i32, [vp, vp, vp, C.c_uint32, vp, vp, vp, u64, vp, vp]),
+        "ipcfp_verify_storage_columns": (i32, [vp, vp, vp, vp, vp]),
+        "ipcfp_expand_storage_claims_device": (i32, [vp, vp, C.c_uint32, vp, vp, vp, u64, vp]),
         "ipcfp_cid_from_string": (i32, [C.c_char_p, vp]),
         "ipcfp_cid_to_slot": (i32, [vp, C.c_uint32, vp]),
         "ipcfp_cid_to_string": (i32, [C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32]),
@@ -860,6 +876,76 @@ def pack_storage_proofs(claims_arr, n: int) -> np.ndarray:
     return out
 
 
+# one record of the run table of the column form (include/ipcfp.h IPCFP_SRUN_*; private to the binding)
+_SRUN_DTYPE = np.dtype([("child_epoch", np.int64), ("actor_id", np.uint64), ("child", np.uint8, (CID_SLOT,)),
+                        ("state_root", np.uint8, (CID_SLOT,)), ("actor_state", np.uint8, (CID_SLOT,)),
+                        ("storage_root", np.uint8, (CID_SLOT,)), ("first_claim", np.uint32), ("n_claims", np.uint32),
+                        ("flags", np.uint32), ("reserved", np.uint32)])
+assert _SRUN_DTYPE.itemsize == 192
+
+
+class StorageColumns:
+    """Storage claims in run-compressed, column form (ipcfp_storage_columns_t): owns the handle; `runs`, `slot`, `value`,
+    `cflags` are numpy views of the handle's memory (valid until close())."""
+
+    def __init__(self, handle):
+        self.lib = load_library()
+        self.h = handle
+        lib = self.lib
+        self.n = int(lib.ipcfp_storage_columns_count(handle))
+        nr = C.c_uint32()
+        pr = lib.ipcfp_storage_columns_runs(handle, C.byref(nr))
+        self.n_runs = int(nr.value)
+        self.nbytes = int(lib.ipcfp_storage_columns_bytes(handle))
+
+        def view(ptr, count, dtype, shape):
+            if not count:
+                return np.zeros(shape, dtype=dtype)
+            buf = (C.c_uint8 * (count * np.dtype(dtype).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dtype).reshape(shape)
+
+        self.runs = view(pr, self.n_runs, _SRUN_DTYPE, (self.n_runs,))
+        self.slot = view(lib.ipcfp_storage_columns_slots(handle), self.n * 32, np.uint8, (self.n, 32))
+        self.value = view(lib.ipcfp_storage_columns_values(handle), self.n * 32, np.uint8, (self.n, 32))
+        self.cflags = view(lib.ipcfp_storage_columns_cflags(handle), self.n, np.uint8, (self.n,))
+
+    def close(self):
+        if self.h:
+            self.runs = self.slot = self.value = self.cflags = None
+            self.lib.ipcfp_storage_columns_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def compact_storage_claims(claims: np.ndarray) -> StorageColumns:
+    """Host-only: SCLAIM_DTYPE[n] → the column form with maximal runs (ipcfp_compact_storage_claims; no GPU)."""
+    lib = load_library()
+    claims = np.ascontiguousarray(claims, dtype=SCLAIM_DTYPE)
+    h = C.c_void_p()
+    rc = lib.ipcfp_compact_storage_claims(_p(claims), len(claims), C.byref(h))
+    if rc != 0:
+        raise EngineError(f"compact_storage_claims: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+    return StorageColumns(h)
+
+
+def expand_storage_claims(cols: StorageColumns) -> np.ndarray:
+    """Host-only: the column form → SCLAIM_DTYPE[n] (ipcfp_expand_storage_claims)."""
+    lib = load_library()
+    out = np.zeros(cols.n, dtype=SCLAIM_DTYPE)
+    rc = lib.ipcfp_expand_storage_claims(cols.h, _p(out))
+    if rc != 0:
+        raise EngineError(f"expand_storage_claims: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+    return out
+
+
 def bundle_check_json(text: bytes, flags: int = 0):
     """Host half of the bundle parse (no GPU): → (ok, n_storage, n_events, n_blocks, error text)."""
     lib = load_library()
@@ -1311,6 +1397,37 @@ class Witness:
         self.eng._check(self.lib.ipcfp_verify_storage_claims_device(
             self.eng.h, self.h, claims_ptr, n, C.cast(C.pointer(trust), C.c_void_p) if trust is not None else None,
             status_ptr), "verify_storage_claims_device")
+
+    def verify_storage_claims(self, claims: np.ndarray, trust=None) -> np.ndarray:
+        """Packed storage claims in HOST memory: upload + verify + status bytes back (PCIe-inclusive)."""
+        claims = np.ascontiguousarray(claims, dtype=SCLAIM_DTYPE)
+        st = np.zeros(len(claims), dtype=np.uint8)
+        self.eng._check(self.lib.ipcfp_verify_storage_claims(
+            self.eng.h, self.h, _p(claims), len(claims), C.cast(C.pointer(trust), C.c_void_p) if trust is not None else None,
+            _p(st)), "verify_storage_claims")
+        return st
+
+    def verify_storage_columns(self, cols: "StorageColumns", trust=None) -> np.ndarray:
+        """The column form in HOST memory (ipcfp_verify_storage_columns): upload, verify, status bytes back."""
+        st = np.zeros(cols.n, dtype=np.uint8)
+        self.eng._check(self.lib.ipcfp_verify_storage_columns(
+            self.eng.h, self.h, cols.h, C.cast(C.pointer(trust), C.c_void_p) if trust is not None else None, _p(st)),
+            "verify_storage_columns")
+        return st
+
+    def verify_storage_columns_device(self, runs_ptr: int, n_runs: int, slot_ptr: int, value_ptr: int, cflags_ptr: int, n: int,
+                                      status_ptr: int, trust=None):
+        """The column form resident in HBM (run table n_runs × 192 bytes, slot / value n × 32, cflags n)."""
+        self.eng._check(self.lib.ipcfp_verify_storage_columns_device(
+            self.eng.h, self.h, runs_ptr or None, int(n_runs), slot_ptr or None, value_ptr or None, cflags_ptr or None, int(n),
+            C.cast(C.pointer(trust), C.c_void_p) if trust is not None else None, status_ptr or None), "verify_storage_columns_device")
+
+    def expand_storage_claims_device(self, runs_ptr: int, n_runs: int, slot_ptr: int, value_ptr: int, cflags_ptr: int, n: int,
+                                     claims_out_ptr: int):
+        """The column form resident in HBM → ipcfp_storage_claim_t[n] at claims_out_ptr (needs no witness: any Witness's engine)."""
+        self.eng._check(self.lib.ipcfp_expand_storage_claims_device(
+            self.eng.h, runs_ptr or None, int(n_runs), slot_ptr or None, value_ptr or None, cflags_ptr or None, int(n),
+            claims_out_ptr or None), "expand_storage_claims_device")
 
     def verify_event_claims_device(self, tipsets: np.ndarray, claims_ptr: int, n: int, blob_ptr: int, blob_len: int,
                                    status_ptr: int, trust=None, filt=None):

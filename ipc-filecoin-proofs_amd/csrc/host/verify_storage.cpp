@@ -47,14 +47,41 @@ static const ipcfp_trust_policy_t kAcceptAll = {0, 0, 0, 0};
 // and the one-lane kernel takes what that leaves pending (an inline small-map layout, a block the table does not cover).
 // A small batch — and everything, with IPCFP_HAMT_TABLE=0 — goes through the one-lane kernel alone.  The table lives
 // for this call only.  One host synchronisation (the number of runs).
-int launch_verify_storage(ipcfp_ctx* ctx, ipcfp_witness* wit, const StorageClaimPacked* claims_d, uint32_t n,
-                          const ipcfp_trust_policy_t& trust, uint8_t* status_d) {
+//
+// The COLUMN form (`cols`: include/ipcfp.h "storage claims in run-compressed, column form") takes the same steps with the
+// column instantiations of the same kernels, minus step 1's discovery: the runs arrive, one kernel checks that they tile
+// [0, n) and writes every claim's run (kernels/storage_columns.hip), StorageRun[n_runs] is sized from the argument, and the
+// table's verdict — a table that does not tile is IPCFP_E_INVALID, no verdicts — is read with the synchronisation the call
+// has anyway.  `wait_upload`: the claims are still crossing PCIe on a thread of their own (host/upload.cpp UploadTask);
+// they are waited for behind the node table's launch, which needs only the witness.
+static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const StorageClaimPacked* claims_d, const StorageColumnsDev* cols,
+                               uint32_t n, const ipcfp_trust_policy_t& trust, uint8_t* status_d, bool wait_upload) {
     if (n == 0) return IPCFP_OK;
     ProfileScope prof(ctx, IPCFP_K_STORAGE_VERIFY);
     const WitnessView w = witness_view(wit);
     const int forced = ctx->hamt_table;  // (env IPCFP_HAMT_TABLE / ipcfp_ctx_set_tuning "hamt_table")
     const bool tabled = forced == 1 || (forced != 0 && uint64_t(n) * 16u >= wit->n);
-    if (!tabled) return launch_verify_storage_lanes(ctx, w, claims_d, n, trust, status_d, 0);
+    ColumnClaimSrc csrc{};
+    if (cols) csrc = ColumnClaimSrc{static_cast<const StorageRunRec*>(cols->runs), cols->slot, cols->value, cols->cflags};
+    DevBuf<uint32_t> run_of, bad_own;
+    uint32_t* bad_d = nullptr;  // the column form: set by k_storage_column_runs where the run table does not tile [0, n)
+    uint32_t bad = 0;
+    if (cols) {
+        IPCFP_HIP(ctx, run_of.alloc(n));
+        IPCFP_HIP(ctx, ctl_words(ctx, bad_own, bad_d, 2, false));
+    }
+    if (!tabled) {
+        if (wait_upload)
+            if (int rc_up = upload_task_wait(ctx)) return rc_up;
+        if (!cols) return launch_verify_storage_lanes(ctx, w, claims_d, n, trust, status_d, 0);
+        // a small batch: every claim by the one-lane kernel, which finds its run's record through run_of — so the table's verdict first
+        int rc_s = launch_storage_column_runs(ctx, *cols, n, run_of.p, nullptr, bad_d);
+        if (rc_s) return rc_s;
+        IPCFP_HIP(ctx, ctl_read(ctx, &bad, bad_d, 4));
+        IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+        if (bad) return set_error(ctx, IPCFP_E_INVALID, "the run table does not tile the %u claims", n);
+        return launch_verify_storage_lanes(ctx, w, csrc, run_of.p, n, trust, status_d, 0);
+    }
     constexpr uint32_t kUndecided = 0xfdu;
     DevBuf<HamtNodeRec> table;
     DevBuf<uint32_t> long_list, long_count;
@@ -137,49 +164,84 @@ int launch_verify_storage(ipcfp_ctx* ctx, ipcfp_witness* wit, const StorageClaim
         }
     }
     if (rc) return rc;
-    DevBuf<uint32_t> flag, pos, run_of;
+    if (wait_upload) {  // (the node table is on its way: from here on the kernels read claims)
+        rc = upload_task_wait(ctx);
+        if (rc) return rc;
+    }
+    DevBuf<uint32_t> flag, pos;
     DevBuf<uint64_t> scratch, total_d;
-    IPCFP_HIP(ctx, flag.alloc(n));
-    IPCFP_HIP(ctx, pos.alloc(n));
-    IPCFP_HIP(ctx, run_of.alloc(n));
-    IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
-    IPCFP_HIP(ctx, total_d.alloc(1));
-    rc = launch_storage_run_flags(ctx, claims_d, n, flag.p);
-    if (rc) return rc;
-    rc = launch_scan_u32(ctx, flag.p, n, pos.p, total_d.p, scratch.p);
-    if (rc) return rc;
+    DevBuf<StorageRun> runs;
     uint64_t n_runs = 0;
-    IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
+    if (cols) {
+        n_runs = cols->n_runs;
+        IPCFP_HIP(ctx, runs.alloc(n_runs));
+        rc = launch_storage_column_runs(ctx, *cols, n, run_of.p, runs.p, bad_d);
+        if (rc) return rc;
+        IPCFP_HIP(ctx, ctl_read(ctx, &bad, bad_d, 4));
+    } else {
+        IPCFP_HIP(ctx, flag.alloc(n));
+        IPCFP_HIP(ctx, pos.alloc(n));
+        IPCFP_HIP(ctx, run_of.alloc(n));
+        IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
+        IPCFP_HIP(ctx, total_d.alloc(1));
+        rc = launch_storage_run_flags(ctx, claims_d, n, flag.p);
+        if (rc) return rc;
+        rc = launch_scan_u32(ctx, flag.p, n, pos.p, total_d.p, scratch.p);
+        if (rc) return rc;
+        IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
+    }
     if (!ring && !early_outline) IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
     IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    if (bad) return set_error(ctx, IPCFP_E_INVALID, "the run table does not tile the %u claims", n);  // (the guards drain the side streams)
     if (!early_outline) {
         rc = queue_outline();
         if (rc) return rc;
     }
     if (aux_guard.armed) IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
-    DevBuf<StorageRun> runs;
-    IPCFP_HIP(ctx, runs.alloc(n_runs));
-    rc = launch_storage_run_heads(ctx, flag.p, pos.p, n, run_of.p, runs.p);
-    if (rc) return rc;
-    rc = launch_storage_run_facts(ctx, w, claims_d, runs.p, uint32_t(n_runs));
+    if (!cols) {
+        IPCFP_HIP(ctx, runs.alloc(n_runs));
+        rc = launch_storage_run_heads(ctx, flag.p, pos.p, n, run_of.p, runs.p);
+        if (rc) return rc;
+    }
+    rc = cols ? launch_storage_run_facts(ctx, w, csrc, runs.p, uint32_t(n_runs)) : launch_storage_run_facts(ctx, w, claims_d, runs.p, uint32_t(n_runs));
     if (rc) return rc;
     // the table is whole from here on
     if (aux_guard.armed) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_event, 0));
     if (outline_event) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_event, 0));
     aux_guard.armed = k1_guard.armed = false;  // the main stream is ordered behind the side kernels now: pool reuse on it is safe
-    rc = launch_storage_run_actors_table(ctx, w, table.p, claims_d, runs.p, uint32_t(n_runs), kUndecided);
+    rc = cols ? launch_storage_run_actors_table(ctx, w, table.p, csrc, runs.p, uint32_t(n_runs), kUndecided)
+              : launch_storage_run_actors_table(ctx, w, table.p, claims_d, runs.p, uint32_t(n_runs), kUndecided);
     if (rc) return rc;
-    rc = launch_storage_run_actors_lane(ctx, w, claims_d, runs.p, uint32_t(n_runs), kUndecided);
+    rc = cols ? launch_storage_run_actors_lane(ctx, w, csrc, runs.p, uint32_t(n_runs), kUndecided)
+              : launch_storage_run_actors_lane(ctx, w, claims_d, runs.p, uint32_t(n_runs), kUndecided);
     if (rc) return rc;
     // the first step of the runs' storage gets, once per run (IPCFP_STORAGE_RUN_CHILDREN=0: every claim by itself)
     static const bool run_children = [] { const char* e = std::getenv("IPCFP_STORAGE_RUN_CHILDREN"); return !(e && std::atoi(e) == 0); }();
     DevBuf<uint32_t> root_children;
-    if (run_children && n_runs) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 34u));
+    // (the column form's claims have no CID to compare with: their run's word is made whatever the switch says, which then only
+    // decides who takes the first step of a get)
+    if ((run_children || cols) && n_runs) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 34u));
+    if (cols) {
+        rc = launch_verify_storage_table(ctx, w, table.p, csrc, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, run_children, trust,
+                                         kUndecided, status_d);
+        if (rc) return rc;
+        return launch_verify_storage_lanes(ctx, w, csrc, run_of.p, n, trust, status_d, 1);
+    }
     rc = launch_verify_storage_table(ctx, w, table.p, claims_d, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, trust, kUndecided,
                                      status_d);
     if (rc) return rc;
     return launch_verify_storage_lanes(ctx, w, claims_d, n, trust, status_d, 1);
     // (the scratch buffers go back to the pool on return; reuse is ordered on the one stream)
+}
+
+int launch_verify_storage(ipcfp_ctx* ctx, ipcfp_witness* wit, const StorageClaimPacked* claims_d, uint32_t n,
+                          const ipcfp_trust_policy_t& trust, uint8_t* status_d) {
+    return verify_storage_impl(ctx, wit, claims_d, nullptr, n, trust, status_d, false);
+}
+
+int launch_verify_storage_columns(ipcfp_ctx* ctx, ipcfp_witness* wit, const StorageColumnsDev& cols, uint32_t n,
+                                  const ipcfp_trust_policy_t& trust, uint8_t* status_d, bool wait_upload) {
+    return verify_storage_impl(ctx, wit, nullptr, &cols, n, trust, status_d, wait_upload);
 }
 
 }  // namespace ipcfp
@@ -248,6 +310,35 @@ int ipcfp_verify_storage_claims_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, con
     int rc = launch_verify_storage(ctx, w, static_cast<const StorageClaimPacked*>(claims_d), uint32_t(n),
                                    trust ? *trust : kAcceptAll, static_cast<uint8_t*>(status_d));
     if (rc) return rc;
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    return IPCFP_OK;
+}
+
+int ipcfp_verify_storage_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipcfp_storage_claim_t* claims, uint64_t n,
+                                const ipcfp_trust_policy_t* trust, ipcfp_status_t* status) {
+    if (!ctx || !w || w->ctx != ctx || (n && (!claims || !status))) return IPCFP_E_INVALID;
+    if (n >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "batch too large");
+    if (n == 0) return IPCFP_OK;
+    IPCFP_ENTER(ctx);
+    DevBuf<StorageClaimPacked> cd;
+    DevBuf<uint8_t> sd;
+    IPCFP_HIP(ctx, cd.alloc(n));
+    IPCFP_HIP(ctx, sd.alloc(n));
+    // the records cross PCIe on a thread of their own while this one queues the node table, which needs only the witness
+    // (the way ipcfp_verify_event_claims_compact sends its claims beside the walk)
+    const size_t bytes = n * sizeof(StorageClaimPacked);
+    IPCFP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (nothing queued earlier may still use the buffers just taken)
+    if (bytes >= (size_t(8) << 20)) ctx->upload_task = upload_task_start(ctx, cd.p, claims, bytes, nullptr, nullptr, 0);
+    int rc = IPCFP_OK;
+    if (!ctx->upload_task) rc = upload(ctx, cd.p, claims, bytes, ctx->stream);
+    if (!rc) rc = verify_storage_impl(ctx, w, cd.p, nullptr, uint32_t(n), trust ? *trust : kAcceptAll, sd.p, true);
+    const int rc_up = upload_task_wait(ctx);  // (whatever happened: the copy must be over before the buffer goes back to the pool)
+    if (rc == IPCFP_OK) rc = rc_up;
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    IPCFP_HIP(ctx, hipMemcpyAsync(status, sd.p, n, hipMemcpyDeviceToHost, ctx->stream));
     IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
     return IPCFP_OK;
 }

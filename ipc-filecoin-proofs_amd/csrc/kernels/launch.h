@@ -82,6 +82,31 @@ int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const v
 int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const StorageClaimPacked* claims_d, uint32_t n,
                                 const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only);
 
+// … the same over the run-compressed column form (storage_runs.h ColumnClaimSrc): the column instantiations of the kernels above
+struct ColumnClaimSrc;
+struct StorageColumnsDev {  // the form resident in HBM (include/ipcfp.h): run table, columns, counts
+    const void* runs;
+    uint32_t n_runs;
+    const uint8_t *slot, *value, *cflags;
+};
+int launch_verify_storage_columns(ipcfp_ctx* ctx, ipcfp_witness* w, const StorageColumnsDev& cols, uint32_t n,
+                                  const ipcfp_trust_policy_t& trust, uint8_t* status_d, bool wait_upload = false);  // host/verify_storage.cpp
+int launch_storage_run_facts(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, void* runs_d, uint32_t n_runs);
+int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, void* runs_d,
+                                    uint32_t n_runs, uint32_t undecided);
+int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, void* runs_d, uint32_t n_runs,
+                                   uint32_t undecided);
+int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, uint32_t n,
+                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut,
+                                const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d);
+int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, const uint32_t* run_of_d, uint32_t n,
+                                const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only);
+// --- storage_columns.hip --- the run table checked (it must tile [0, n): *bad_d |= 1 where it does not) and laid out per claim:
+// run_of_d[t] = claim t's run for every run that is sound; runs_d (nullable): StorageRun[n_runs], first_claim set
+int launch_storage_column_runs(ipcfp_ctx* ctx, const StorageColumnsDev& cols, uint32_t n, uint32_t* run_of_d, void* runs_d, uint32_t* bad_d);
+// columns → StorageClaimPacked[n] (run_of_d as filled above)
+int launch_expand_storage_columns(ipcfp_ctx* ctx, const StorageColumnsDev& cols, uint32_t n, const uint32_t* run_of_d, void* claims_out_d);
+
 // --- claims_compact.hip --- compact event claims → EventClaimPacked[n] + blob; scratch_u32: 4 n words, scan_scratch: div_up(n, 1024) + 2
 // u64 whose LAST word receives the packed blob's length
 int launch_expand_claims(ipcfp_ctx* ctx, const void* compact_d, uint32_t n, const ipcfp_event_claim_group_t* groups_d, uint32_t n_groups,

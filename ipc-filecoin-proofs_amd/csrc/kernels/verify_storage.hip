@@ -31,7 +31,9 @@ __device__ __forceinline__ bool trusted(const ipcfp_trust_policy_t& t, long long
     return epoch >= t.min_epoch && epoch <= t.max_epoch;  // cert.rs:60-63
 }
 
-__device__ __forceinline__ uint32_t verify_storage_one(const WitnessView& w, const StorageClaimPacked& c,
+// (Claim: StorageClaimPacked, or the column form's view of a run record + the columns — storage_runs.h)
+template <class Claim>
+__device__ __forceinline__ uint32_t verify_storage_one(const WitnessView& w, const Claim& c,
                                                        const ipcfp_trust_policy_t& trust) {
     // Step 2: verify_trust_anchor (storage/verifier.rs:81-92)
     if (!(c.flags & SC_CHILD_PARSED)) return IPCFP_ST_ERR_BAD_CLAIM;             // :85
@@ -71,14 +73,14 @@ __device__ __forceinline__ uint32_t verify_storage_one(const WitnessView& w, con
 // WAVES = wavefronts per SIMD the register allocator must leave room for.  verify_storage_one inlines six
 // layout attempts, each a Keccak + SHA-256 + HAMT walk: at 4 waves (128 VGPRs) it spills 384 bytes per
 // lane to scratch, at 3 waves (168 VGPRs) it does not.  IPCFP_STORAGE_WAVES selects (default: see launch).
-template <int WAVES>
-__global__ __launch_bounds__(256, WAVES) void k_verify_storage(WitnessView w, const StorageClaimPacked* __restrict__ claims,
+template <int WAVES, class Src>
+__global__ __launch_bounds__(256, WAVES) void k_verify_storage(WitnessView w, Src src, const uint32_t* __restrict__ run_of,
                                                                uint32_t n, ipcfp_trust_policy_t trust,
                                                                uint8_t* __restrict__ status, int pending_only) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
     if (pending_only && status[t] != kStPending) return;  // settled from the node table (k_verify_storage_table)
-    status[t] = uint8_t(verify_storage_one(w, claims[t], trust));
+    status[t] = uint8_t(verify_storage_one(w, src.claim(t, run_of), trust));  // (run_of: the column form's; null for plain claims)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -107,12 +109,13 @@ __global__ __launch_bounds__(256) void k_storage_run_heads(const uint32_t* __res
     if (flag[t]) runs[r].first_claim = t;
 }
 
-__global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_facts(WitnessView w, const StorageClaimPacked* __restrict__ claims,
+template <class Src>
+__global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_facts(WitnessView w, Src src,
                                                                              StorageRun* __restrict__ runs, uint32_t n_runs) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_runs) return;
     StorageRun run = runs[i];
-    const StorageClaimPacked& c = claims[run.first_claim];
+    const auto& c = src.run_key(i, run.first_claim);  // the run's first claim, or its record of the run table
     // verify_parent_state_root (storage/verifier.rs:95-111): the child header
     HeaderLite hdr;
     uint32_t hb;
@@ -147,14 +150,15 @@ __global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_facts(Wit
 }
 
 // get_actor_state's HAMT half for the runs k_storage_run_actors_table left undecided (a block the table does not cover)
-__global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_actors_lane(WitnessView w, const StorageClaimPacked* __restrict__ claims,
+template <class Src>
+__global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_actors_lane(WitnessView w, Src src,
                                                                                    StorageRun* __restrict__ runs, uint32_t n_runs,
                                                                                    uint32_t undecided) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_runs) return;
     if (runs[i].sr_status != IPCFP_ST_TRUE || runs[i].actor_status != undecided) return;
     uint8_t key[12];
-    const uint32_t kl = id_address_bytes(claims[runs[i].first_claim].actor_id, key);  // common/decode.rs:34
+    const uint32_t kl = id_address_bytes(src.run_key(i, runs[i].first_claim).actor_id, key);  // common/decode.rs:34
     ValueLoc loc;
     uint32_t st = hamt_get(w, runs[i].actors, 5, VK_ACTOR_STATE, key, kl, loc);         // decode.rs:29-37
     CidKey actor_state{};
@@ -172,25 +176,33 @@ __global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_storage_run_actors_la
     runs[i].actor_state = actor_state;
 }
 
-int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const void* claims_d, void* runs_d, uint32_t n_runs,
-                                   uint32_t undecided) {
+template <class Src>
+static int run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const Src& src, void* runs_d, uint32_t n_runs, uint32_t undecided) {
     if (n_runs == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_storage_run_actors_lane, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w,
-                       static_cast<const StorageClaimPacked*>(claims_d), static_cast<StorageRun*>(runs_d), n_runs, undecided);
+    hipLaunchKernelGGL(k_storage_run_actors_lane<Src>, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w, src,
+                       static_cast<StorageRun*>(runs_d), n_runs, undecided);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
+}
+int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const void* claims_d, void* runs_d, uint32_t n_runs,
+                                   uint32_t undecided) {
+    return run_actors_lane(ctx, w, PlainClaimSrc{static_cast<const StorageClaimPacked*>(claims_d)}, runs_d, n_runs, undecided);
+}
+int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, void* runs_d, uint32_t n_runs,
+                                   uint32_t undecided) {
+    return run_actors_lane(ctx, w, cols, runs_d, n_runs, undecided);
 }
 
 // get_actor_state's HAMT half over the node table (hamt_table.h), one run per lane; what the table does not cover stays
 // `undecided` for k_storage_run_actors_lane
-__global__ __launch_bounds__(256) void k_storage_run_actors_table(WitnessView w, const HamtNodeRec* __restrict__ table,
-                                                                  const StorageClaimPacked* __restrict__ claims,
+template <class Src>
+__global__ __launch_bounds__(256) void k_storage_run_actors_table(WitnessView w, const HamtNodeRec* __restrict__ table, Src src,
                                                                   StorageRun* __restrict__ runs, uint32_t n_runs, uint32_t undecided) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_runs) return;
     if (runs[i].sr_status != IPCFP_ST_TRUE) return;
     uint8_t key[12];
-    const uint32_t kl = id_address_bytes(claims[runs[i].first_claim].actor_id, key);  // common/decode.rs:34
+    const uint32_t kl = id_address_bytes(src.run_key(i, runs[i].first_claim).actor_id, key);  // common/decode.rs:34
     ValueLoc loc;
     uint32_t st = table_hamt_get(w, table, runs[i].actors, 5, HK_ACTOR_STATE, key, kl, loc);  // decode.rs:29-37
     CidKey actor_state{};
@@ -214,9 +226,10 @@ __global__ __launch_bounds__(256) void k_storage_run_actors_table(WitnessView w,
 // link's 38 bytes, probed the index and compared a CID — three dependent random reads of its ≈ eight — for an answer its
 // run's neighbours had found already.  32 lanes per run; kNoBlock where the table has no record of the root, the pointer is
 // not a standard link or the block is missing (the claim's own lane then takes the long way and gives the status).
+template <class Src>
 __global__ __launch_bounds__(256) void k_storage_run_children(WitnessView w, const HamtNodeRec* __restrict__ table,
-                                                              const StorageRun* __restrict__ runs, uint32_t n_runs,
-                                                              const StorageClaimPacked* __restrict__ claims,
+                                                              const StorageRun* __restrict__ runs, uint32_t n_runs, Src src,
+                                                              ipcfp_trust_policy_t trust,
                                                               uint32_t* __restrict__ root_block, uint32_t* __restrict__ run_match,
                                                               uint32_t* __restrict__ root_child) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, i = t >> 5, p = t & 31u;
@@ -225,9 +238,17 @@ __global__ __launch_bounds__(256) void k_storage_run_children(WitnessView w, con
         // The three CID comparisons of steps 3-5 (storage/verifier.rs:110, :126, :144) are the same for every claim of a run — a
         // run IS "same child, state root, actor, actor state, storage root" (same_run) — so they are made here, on the run's
         // first claim; each claim still answers for its own strings' canonical form (flags).
-        const StorageClaimPacked& c = claims[runs[i].first_claim];
-        run_match[i] = (cid_equal(runs[i].parent_state_root, c.state_root) ? 1u : 0u) | (cid_equal(runs[i].actor_state, c.actor_state) ? 2u : 0u) |
-                       (cid_equal(runs[i].contract_state, c.storage_root) ? 4u : 0u);
+        const auto& c = src.run_key(i, runs[i].first_claim);
+        uint32_t m = (cid_equal(runs[i].parent_state_root, c.state_root) ? 1u : 0u) | (cid_equal(runs[i].actor_state, c.actor_state) ? 2u : 0u) |
+                     (cid_equal(runs[i].contract_state, c.storage_root) ? 4u : 0u);
+        if constexpr (Src::kColumns) {
+            // … and, on the column route, the rest of what the run's record says for all of its claims (storage_runs.h RM_*): a claim
+            // then reads this word and never the 192-byte record
+            m |= (c.flags & IPCFP_SRUN_FLAG_MASK) << RM_FLAGS_SHIFT;
+            if (trusted(trust, c.child_epoch)) m |= RM_TRUSTED;
+            if ((c.flags & ~IPCFP_SRUN_FLAG_MASK) || c.reserved) m |= RM_BAD_RECORD;
+        }
+        run_match[i] = m;
     }
     uint32_t rb = kNoBlock, child = kNoBlock;
     if (runs[i].root_kind == 3) {
@@ -382,8 +403,15 @@ __device__ __forceinline__ bool left_pad_32_staged(const ValueStage& vs, uint32_
 // (Seven wavefronts per SIMD asked of the allocator: 72 VGPRs and 48 more bytes of scratch against its own 83 and five.  The
 // kernel is a long instruction stream with 116 loads per wavefront that depend on each other; more wavefronts in flight
 // were 2.13 → 2.02 ms for configs[4]'s call — 6: 2.05, 8: 2.03; profiles/r06_experiments.md.)
+//
+// Column source (storage_runs.h ColumnClaimSrc): the lane's slot and value are two 16-byte loads each from slot + 32 t and
+// value + 32 t — a wavefront reads 2 KB of contiguous bytes per column, 16 lines where the 248-byte records are 64 — plus one
+// byte of cflags; everything its run says for it (CID flag bits, the trust policy's answer for the run's epoch, the three
+// CID comparisons of :110, :126, :144) is the run's RM_* word, made once per run by k_storage_run_children.  No CID is
+// compared per claim.  The order of checks is the same; a record or a byte with unknown bits is ERR_BAD_CLAIM.
+template <class Src>
 __global__ __launch_bounds__(256, 7) void k_verify_storage_table(WitnessView w, const HamtNodeRec* __restrict__ table,
-                                                              const StorageClaimPacked* __restrict__ claims, uint32_t n,
+                                                              Src src, uint32_t n,
                                                               const uint32_t* __restrict__ run_of, const StorageRun* __restrict__ runs,
                                                               const uint32_t* __restrict__ root_block, const uint32_t* __restrict__ run_match,
                                                               const uint32_t* __restrict__ root_child, ipcfp_trust_policy_t trust, uint32_t undecided, uint8_t* __restrict__ status) {
@@ -392,37 +420,64 @@ __global__ __launch_bounds__(256, 7) void k_verify_storage_table(WitnessView w, 
 #if IPCFP_VS_STAGE
     __shared__ ValueStage vstage;
 #endif
-    const StorageClaimPacked& c = claims[t];
     const uint32_t ri = run_of[t];
     const StorageRun& run = runs[ri];
-    const uint32_t flags = c.flags;
+    const uint32_t match = run_match ? run_match[ri] : 8u;  // (8: nobody has compared for the run)
+    uint32_t flags;
+    const uint8_t *slot_p, *value_p;
+    bool known = true;
+    if constexpr (Src::kColumns) {
+        const uint32_t cf = src.cflags[t];
+        known = !(match & RM_BAD_RECORD) && !(cf & ~IPCFP_SCOL_FLAG_MASK);
+        flags = ((match >> RM_FLAGS_SHIFT) & IPCFP_SRUN_FLAG_MASK) | cf;
+        slot_p = src.slot + 32ull * t;
+        value_p = src.value + 32ull * t;
+    } else {
+        const StorageClaimPacked& c = src.claims[t];
+        flags = c.flags;
+        slot_p = c.slot;
+        value_p = c.value;
+    }
+    auto child_trusted = [&] {
+        if constexpr (Src::kColumns) return (match & RM_TRUSTED) != 0u;
+        else return trusted(trust, src.claims[t].child_epoch);
+    };
+    // (the plain source's three CID slots, read only where nobody has compared for the run)
+    auto claimed_equal = [&](const CidKey& derived, int which, uint32_t bit) {
+        if constexpr (Src::kColumns) {
+            return (match & bit) != 0u;
+        } else {
+            const StorageClaimPacked& c = src.claims[t];
+            return match & 8u ? cid_equal(derived, which == 0 ? c.state_root : which == 1 ? c.actor_state : c.storage_root) : (match & bit) != 0u;
+        }
+    };
     // everything of the claim that is used late — the slot (hash, bucket compare) and the value (the last compare) — now, with
     // the lines that hold the CIDs: by the time the walk is done the L2 has long dropped them
     uint64_t kw[4], cv[4];
 #if IPCFP_VS_PRELOAD
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        kw[j] = reinterpret_cast<const uint64_t*>(c.slot)[j];
-        cv[j] = reinterpret_cast<const uint64_t*>(c.value)[j];
+        kw[j] = reinterpret_cast<const uint64_t*>(slot_p)[j];
+        cv[j] = reinterpret_cast<const uint64_t*>(value_p)[j];
     }
 #endif
     uint32_t st = kStPending;
-    const uint32_t match = run_match ? run_match[ri] : 8u;  // (8: nobody has compared for the run)
     do {
+        if (!known) { st = IPCFP_ST_ERR_BAD_CLAIM; break; }                                               // (column form: bits nobody knows)
         // Step 2: verify_trust_anchor (storage/verifier.rs:81-92)
         if (!(flags & SC_CHILD_PARSED)) { st = IPCFP_ST_ERR_BAD_CLAIM; break; }                           // :85
-        if (!trusted(trust, c.child_epoch)) { st = IPCFP_ST_FALSE_UNTRUSTED_CHILD; break; }               // :87
+        if (!child_trusted()) { st = IPCFP_ST_FALSE_UNTRUSTED_CHILD; break; }                               // :87
         // Step 3: verify_parent_state_root (:95-111)
         if (run.hdr_status != IPCFP_ST_TRUE) { st = run.hdr_status; break; }                              // :101-107
-        if (!((flags & SC_STATE_ROOT_CANON) && (match & 8u ? cid_equal(run.parent_state_root, c.state_root) : (match & 1u) != 0u))) { st = IPCFP_ST_FALSE_STATE_ROOT; break; }  // :110
+        if (!((flags & SC_STATE_ROOT_CANON) && claimed_equal(run.parent_state_root, 0, 1u))) { st = IPCFP_ST_FALSE_STATE_ROOT; break; }  // :110
         // Step 4: verify_actor_state (:114-127)
         if (run.sr_status != IPCFP_ST_TRUE) { st = run.sr_status; break; }                                // decode.rs:23-26
         if (run.actor_status == undecided) break;                                                         // (pending)
         if (run.actor_status != IPCFP_ST_TRUE) { st = run.actor_status; break; }                          // :122
-        if (!((flags & SC_ACTOR_STATE_CANON) && (match & 8u ? cid_equal(run.actor_state, c.actor_state) : (match & 2u) != 0u))) { st = IPCFP_ST_FALSE_ACTOR_STATE; break; }  // :126
+        if (!((flags & SC_ACTOR_STATE_CANON) && claimed_equal(run.actor_state, 1, 2u))) { st = IPCFP_ST_FALSE_ACTOR_STATE; break; }  // :126
         // Step 5: verify_storage_root (:130-145)
         if (run.evm_status != IPCFP_ST_TRUE) { st = run.evm_status; break; }                              // :136-141
-        if (!((flags & SC_STORAGE_ROOT_CANON) && (match & 8u ? cid_equal(run.contract_state, c.storage_root) : (match & 4u) != 0u))) { st = IPCFP_ST_FALSE_STORAGE_ROOT; break; }  // :144
+        if (!((flags & SC_STORAGE_ROOT_CANON) && claimed_equal(run.contract_state, 2, 4u))) { st = IPCFP_ST_FALSE_STORAGE_ROOT; break; }  // :144
         // Step 6: verify_storage_value (:148-170)
         if (!(flags & SC_SLOT_PARSED)) { st = IPCFP_ST_ERR_BAD_CLAIM; break; }                            // :155-157
         if (run.root_kind == 4) { st = IPCFP_ST_ERR_MISSING_BLOCK; break; }                               // decode.rs:41-43
@@ -431,11 +486,11 @@ __global__ __launch_bounds__(256, 7) void k_verify_storage_table(WitnessView w, 
         ValueLoc loc;
 #if !IPCFP_VS_PRELOAD
         {
-            const Raw16 a = raw_ld128(c.slot), b = raw_ld128(c.slot + 16);
+            const Raw16 a = raw_ld128(slot_p), b = raw_ld128(slot_p + 16);
             kw[0] = a.lo, kw[1] = a.hi, kw[2] = b.lo, kw[3] = b.hi;
         }
 #endif
-        const uint32_t hs = table_hamt_get(w, table, run.hamt_root, run.hamt_bw, HK_VEC_U8, c.slot, 32, loc,  // decode.rs:79-96
+        const uint32_t hs = table_hamt_get(w, table, run.hamt_root, run.hamt_bw, HK_VEC_U8, slot_p, 32, loc,  // decode.rs:79-96
                                            root_block ? root_block[ri] : kNoBlock, root_child ? root_child + size_t(ri) * 32u : nullptr, kw);
         if (hs == kTablePunt) break;
         if (hs != IPCFP_ST_NOT_FOUND) {  // unwrap_or_default(): a missing key means zero
@@ -470,7 +525,7 @@ __global__ __launch_bounds__(256, 7) void k_verify_storage_table(WitnessView w, 
         if (!(flags & SC_VALUE_MATCHABLE)) { st = IPCFP_ST_FALSE_VALUE; break; }  // can never equal "0x" + 64 hex digits
 #if !IPCFP_VS_PRELOAD
         {
-            const Raw16 a = raw_ld128(c.value), b = raw_ld128(c.value + 16);
+            const Raw16 a = raw_ld128(value_p), b = raw_ld128(value_p + 16);
             cv[0] = a.lo, cv[1] = a.hi, cv[2] = b.lo, cv[3] = b.hi;
         }
 #endif
@@ -480,31 +535,54 @@ __global__ __launch_bounds__(256, 7) void k_verify_storage_table(WitnessView w, 
     status[t] = uint8_t(st);
 }
 
-int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const void* claims_d, void* runs_d,
-                                    uint32_t n_runs, uint32_t undecided) {
+template <class Src>
+static int run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const Src& src, void* runs_d, uint32_t n_runs,
+                            uint32_t undecided) {
     if (n_runs == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_storage_run_actors_table, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w,
-                       static_cast<const HamtNodeRec*>(table_d), static_cast<const StorageClaimPacked*>(claims_d),
-                       static_cast<StorageRun*>(runs_d), n_runs, undecided);
+    hipLaunchKernelGGL(k_storage_run_actors_table<Src>, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w,
+                       static_cast<const HamtNodeRec*>(table_d), src, static_cast<StorageRun*>(runs_d), n_runs, undecided);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
+int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const void* claims_d, void* runs_d,
+                                    uint32_t n_runs, uint32_t undecided) {
+    return run_actors_table(ctx, w, table_d, PlainClaimSrc{static_cast<const StorageClaimPacked*>(claims_d)}, runs_d, n_runs, undecided);
+}
+int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, void* runs_d,
+                                    uint32_t n_runs, uint32_t undecided) {
+    return run_actors_table(ctx, w, table_d, cols, runs_d, n_runs, undecided);
+}
 // root_children_d: n_runs × 34 words of scratch (block of every run's root, the runs' CID matches, then 32 children per run), or null: every claim resolves its own
-int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const void* claims_d, uint32_t n,
-                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d,
-                                const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d) {
+// shortcut = false (column route only): the per-run words are made all the same — its claims have nothing else to compare with —
+// and every claim takes its own first step
+template <class Src>
+static int verify_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const Src& src, uint32_t n, const uint32_t* run_of_d,
+                        const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut, const ipcfp_trust_policy_t& trust,
+                        uint32_t undecided, uint8_t* status_d) {
     uint32_t* root_block = root_children_d;
     uint32_t* run_match = root_children_d ? root_children_d + n_runs : nullptr;
     uint32_t* root_child = root_children_d ? root_children_d + 2 * size_t(n_runs) : nullptr;
     if (root_children_d && n_runs)
-        hipLaunchKernelGGL(k_storage_run_children, dim3(div_up(n_runs * 32u, 256)), dim3(256), 0, ctx->stream, w,
-                           static_cast<const HamtNodeRec*>(table_d), static_cast<const StorageRun*>(runs_d), n_runs,
-                           static_cast<const StorageClaimPacked*>(claims_d), root_block, run_match, root_child);
-    hipLaunchKernelGGL(k_verify_storage_table, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w,
-                       static_cast<const HamtNodeRec*>(table_d), static_cast<const StorageClaimPacked*>(claims_d), n, run_of_d,
-                       static_cast<const StorageRun*>(runs_d), root_block, run_match, root_child, trust, undecided, status_d);
+        hipLaunchKernelGGL(k_storage_run_children<Src>, dim3(div_up(uint64_t(n_runs) * 32u, 256)), dim3(256), 0, ctx->stream, w,
+                           static_cast<const HamtNodeRec*>(table_d), static_cast<const StorageRun*>(runs_d), n_runs, src, trust, root_block,
+                           run_match, root_child);
+    hipLaunchKernelGGL(k_verify_storage_table<Src>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w,
+                       static_cast<const HamtNodeRec*>(table_d), src, n, run_of_d, static_cast<const StorageRun*>(runs_d),
+                       shortcut ? root_block : nullptr, run_match, shortcut ? root_child : nullptr, trust, undecided, status_d);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
+}
+int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const void* claims_d, uint32_t n,
+                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d,
+                                const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d) {
+    return verify_table(ctx, w, table_d, PlainClaimSrc{static_cast<const StorageClaimPacked*>(claims_d)}, n, run_of_d, runs_d, n_runs,
+                        root_children_d, true, trust, undecided, status_d);
+}
+int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, uint32_t n,
+                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut,
+                                const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d) {
+    if (!root_children_d) return set_error(ctx, IPCFP_E_INVALID, "the column route needs its per-run words");
+    return verify_table(ctx, w, table_d, cols, n, run_of_d, runs_d, n_runs, root_children_d, shortcut, trust, undecided, status_d);
 }
 
 int launch_storage_run_flags(ipcfp_ctx* ctx, const void* claims_d, uint32_t n, uint32_t* flag_d) {
@@ -519,28 +597,45 @@ int launch_storage_run_heads(ipcfp_ctx* ctx, const uint32_t* flag_d, const uint3
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
-int launch_storage_run_facts(ipcfp_ctx* ctx, const WitnessView& w, const void* claims_d, void* runs_d, uint32_t n_runs) {
+template <class Src>
+static int run_facts(ipcfp_ctx* ctx, const WitnessView& w, const Src& src, void* runs_d, uint32_t n_runs) {
     if (n_runs == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_storage_run_facts, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w,
-                       static_cast<const StorageClaimPacked*>(claims_d), static_cast<StorageRun*>(runs_d), n_runs);
+    hipLaunchKernelGGL(k_storage_run_facts<Src>, dim3(div_up(n_runs, 256)), dim3(256), 0, ctx->stream, w, src,
+                       static_cast<StorageRun*>(runs_d), n_runs);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
+int launch_storage_run_facts(ipcfp_ctx* ctx, const WitnessView& w, const void* claims_d, void* runs_d, uint32_t n_runs) {
+    return run_facts(ctx, w, PlainClaimSrc{static_cast<const StorageClaimPacked*>(claims_d)}, runs_d, n_runs);
+}
+int launch_storage_run_facts(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, void* runs_d, uint32_t n_runs) {
+    return run_facts(ctx, w, cols, runs_d, n_runs);
+}
 
 // the one-lane kernel over the whole batch (pending_only = 0) or over what the run / group kernels left kStPending
-int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const StorageClaimPacked* claims_d, uint32_t n,
-                                const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only) {
+template <class Src>
+static int verify_lanes(ipcfp_ctx* ctx, const WitnessView& w, const Src& src, const uint32_t* run_of_d, uint32_t n,
+                        const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only) {
     static const int waves = [] {
         const char* e = std::getenv("IPCFP_STORAGE_WAVES");
         const int v = e ? std::atoi(e) : 4;
         return v >= 2 && v <= 4 ? v : 4;
     }();
     const dim3 g(div_up(n, 256)), blk(256);
-    if (waves == 2) hipLaunchKernelGGL(k_verify_storage<2>, g, blk, 0, ctx->stream, w, claims_d, n, trust, status_d, pending_only);
-    else if (waves == 3) hipLaunchKernelGGL(k_verify_storage<3>, g, blk, 0, ctx->stream, w, claims_d, n, trust, status_d, pending_only);
-    else hipLaunchKernelGGL(k_verify_storage<4>, g, blk, 0, ctx->stream, w, claims_d, n, trust, status_d, pending_only);
+    if (waves == 2) hipLaunchKernelGGL((k_verify_storage<2, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
+    else if (waves == 3) hipLaunchKernelGGL((k_verify_storage<3, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
+    else hipLaunchKernelGGL((k_verify_storage<4, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
+}
+int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const StorageClaimPacked* claims_d, uint32_t n,
+                                const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only) {
+    return verify_lanes(ctx, w, PlainClaimSrc{claims_d}, nullptr, n, trust, status_d, pending_only);
+}
+// (the column form: run_of_d[t] = claim t's run, filled by launch_storage_column_runs)
+int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, const uint32_t* run_of_d, uint32_t n,
+                                const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only) {
+    return verify_lanes(ctx, w, cols, run_of_d, n, trust, status_d, pending_only);
 }
 
 }  // namespace ipcfp
