@@ -143,7 +143,8 @@ int ipcfp_abi_version(void);
 void* ipcfp_ctx_stream(ipcfp_ctx_t* ctx);
 int ipcfp_ctx_sync(ipcfp_ctx_t* ctx);
 /* Route selection (A/B measurements; tests that drive both routes of an entry point over one corpus).  Outcomes never
- * depend on it — every fast route only ever answers what the general one would.  Keys:
+ * depend on it — every fast route only ever answers what the general one would.  This call is the only way to select
+ * these routes (no environment variable does); an unknown key is IPCFP_E_INVALID.  Keys (-1 restores the default):
  *   "hamt_levels"  -1 default (ipcfp_hamt_get*: level by level for batches of >= 1024 queries), 0 per-query walker only,
  *                  k > 0 exactly k levels whatever the batch size
  *   "hamt_coop"    0: the level path decodes ActorState nodes with one lane each instead of sixteen

@@ -56,9 +56,6 @@ struct ipcfp_ctx {
     std::string last_error;
     hipDeviceProp_t props{};
     ipcfp::DevPool pool;
-    // --- tuning knobs (env IPCFP_B2B_MODE / IPCFP_B2B_WG; defaults are the measured best) ---
-    int b2b_mode = 0;        // 0: hipcc-chosen u64 adds, 1: explicit add_co/addc pairs
-    uint32_t b2b_wg = 64;    // K1 workgroup size (multiple of 64, <= 256)
     // --- per-kernel HIP-event timing (ipcfp_profile_*) ---
     bool profiling = false;
     int profile_only = -1;  // >= 0: bracket launches of this kernel id alone (the timed region of bench.py: K1)
@@ -133,28 +130,7 @@ struct ipcfp_ctx {
     unsigned long long mailbox_seq = 0;
     hipEvent_t main_event = nullptr;            // aux stream ← main stream dependency (host/verify_fast.cpp)
     hipEvent_t rehash_event = nullptr;          // main stream ← the deferred TxMeta re-hashes on the aux stream (verify_fast.cpp)
-    // --- reserved CUs (env IPCFP_RESERVE_CUS = CUs per XCD, 0 = off; host/context.cpp): the latency-bound head of a
-    // verify call — tipset prologue, AMT roots, the narrow interior levels — runs on a stream confined to the reserved
-    // CUs while the two side streams (K1, the block-order event parse) are confined to all the others, so those few
-    // wavefronts never share a SIMD's issue slots with the hash or the parse ---
-    hipStream_t stream_narrow = nullptr;        // null: no reservation (the head runs on `stream`)
-    // --- the head stream (env IPCFP_HEAD_STREAM=1; measured and off by default): a verify call's tipset prologue runs here, beside the CID
-    // index's inserts on the main stream instead of behind them (its lookups wait for their keys: tipset_prepare.hip
-    // LiveIndex).  `ctl_event`: the main stream's last re-initialisation of the control block, which the head waits for ---
-    hipStream_t stream_head = nullptr;
-    hipEvent_t ctl_event = nullptr;
-    hipEvent_t head_event = nullptr;            // head stream → main stream hand-back
-    hipEvent_t narrow_event = nullptr;          // main stream ↔ narrow stream hand-overs
-    uint32_t narrow_max_wg = 64;                // a level of at most this many workgroups counts as narrow
-    bool k1_after_be = false;                   // env IPCFP_K1_AFTER_BE: K1 is queued behind the block-order event parse
-    // --- K1 queued late (env IPCFP_K1_DEFER, host/witness.cpp k1_flush): ipcfp_witness_verify_cids_async only notes the
-    // request; the event-verify call that follows queues the launch at the point of ITS kernel sequence where the hash
-    // kernel costs the critical path least (1: behind the AMT walk, 2: before the verify kernel, 3: behind it).  Every
-    // entry point that reads K1's results, synchronises the context or rebuilds the index queues a noted launch first.
-    int k1_defer = 0;
-    bool k1_gate = false;                       // env IPCFP_K1_GATE: … and K1's stream WAITS for the main stream to get there
-    hipEvent_t k1_gate_event = nullptr;
-    struct ipcfp_witness* k1_deferred_w = nullptr;
+    hipEvent_t outline_event = nullptr;         // main stream ← K1 stream: the storage call's outline of the long blocks (host/verify_storage.cpp; created on first use)
     // --- scratch of the ASYNCHRONOUS batch gets (ipcfp_hamt_get_device: node records, work lists, key hashes).  Owned by
     // the context and only ever grown: the kernels of a call that has already returned may still be reading it, and the
     // next call's kernels follow them on the same stream (a pooled buffer would go back to the pool on return) ---
@@ -162,7 +138,6 @@ struct ipcfp_ctx {
     void* scan_scratch = nullptr;
     size_t scan_scratch_bytes = 0;
     unsigned long long scan_epoch = 0;
-    int scan_fused = -1;   // 0: the scan's tail as separate launches with read-back copies (round 3's)
     int hamt_levels = -1;  // -1: level by level for batches of >= 1024 queries; 0: the per-query walker alone; k > 0: exactly k levels
     int hamt_coop = -1;    // 0: the level path parses every node with one lane (kernels/hamt_levels.hip k_hamt_lv_parse) also for ActorState trees
     int hamt_table = -1;   // 1: tabulate EVERY block first (hamt_table.h; A/B measurements)
@@ -178,7 +153,6 @@ struct ipcfp_ctx {
 namespace ipcfp {
 
 int set_error(ipcfp_ctx* ctx, int rc, const char* fmt, ...);
-int k1_flush(ipcfp_ctx* ctx, bool gated = false);  // queue the noted K1 launch, if any (host/witness.cpp)
 
 #define IPCFP_HIP(ctx, call)                                                                    \
     do {                                                                                        \
@@ -214,7 +188,6 @@ inline void ctl_preprime(ipcfp_ctx* ctx) {
     if (!ctx->ctl_dev || ctx->ctl_preprimed || ctx->call_depth != 1) return;
     if (hipMemcpyAsync(ctx->ctl_dev, ctx->ctl_host, 2 * kCtlHalf, hipMemcpyHostToDevice, ctx->stream) == hipSuccess) {
         ctx->ctl_preprimed = true;
-        if (ctx->ctl_event) (void)hipEventRecord(ctx->ctl_event, ctx->stream);
     }
 }
 // Queue ONE read-back of the whole block on the main stream; after sync_stream every word is available through ctl_value.
@@ -271,7 +244,6 @@ inline hipError_t sync_stream(ipcfp_ctx* ctx, hipStream_t s, bool last_of_call =
     if (last_of_call && s == ctx->stream && ctx->ctl_dev && ctx->ctl_primed && !ctx->ctl_preprimed && ctx->call_depth == 1 &&
         hipMemcpyAsync(ctx->ctl_dev, ctx->ctl_host, 2 * kCtlHalf, hipMemcpyHostToDevice, ctx->stream) == hipSuccess) {
         ctx->ctl_preprimed = true;
-        if (ctx->ctl_event) (void)hipEventRecord(ctx->ctl_event, ctx->stream);
     }
     const hipError_t e = wait_stream(ctx, s);
     if (ctl) {
@@ -299,6 +271,7 @@ inline hipError_t sync_stream(ipcfp_ctx* ctx, hipStream_t s, bool last_of_call =
 // Pageable (or pinned) host memory → HBM, stream-ordered on `s`; large transfers are staged by several threads
 // through the context's pinned ring (host/upload.cpp).
 int upload(ipcfp_ctx* ctx, void* dst_d, const void* src, size_t bytes, hipStream_t s);
+bool upload_ring_mode();  // env IPCFP_UPLOAD_MODE=1: large transfers go through the ring instead of the runtime's blocking copy
 UploadTask* upload_task_start(ipcfp_ctx* ctx, void* dst0, const void* src0, size_t bytes0, void* dst1, const void* src1, size_t bytes1);
 int upload_task_wait(ipcfp_ctx* ctx);
 // the claims a verify kernel is about to read are in HBM in the form it reads: the upload beside the walk is over
@@ -477,15 +450,6 @@ struct ipcfp_witness {
     // CID → block-id index (K4)
     ipcfp::DevBuf<uint32_t> index_slots;  // table of block ids, 0xffffffff = empty
     uint32_t index_mask = 0;
-    // the fill in progress (kernels/cid_index.hip): workgroups of k_index_insert that have finished / that there are, and
-    // the point of the main stream where the table was cleared (a lookup on another stream may start from there: the
-    // tipset prologue on the head stream, host/verify_fast.cpp)
-    ipcfp::DevBuf<uint32_t> index_done;
-    uint32_t index_wgs = 0;
-    hipEvent_t index_event = nullptr;
-    ~ipcfp_witness() {
-        if (index_event) (void)hipEventDestroy(index_event);
-    }
     bool uniform_chunks = false;  // every block has the same chunk count → identity order
     // a shard of one tipset (host/shard.cpp): enumerations of a receipts AMT are restricted to [receipt_lo, receipt_hi)
     uint64_t receipt_lo = 0, receipt_hi = ~0ULL;

@@ -182,9 +182,6 @@ int ipcfp_witness_put_keyed(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t*
     w->counters.swap(nw->counters);
     w->index_slots.swap(nw->index_slots);
     w->index_mask = nw->index_mask;
-    w->index_done.swap(nw->index_done);
-    std::swap(w->index_wgs, nw->index_wgs);
-    std::swap(w->index_event, nw->index_event);
     w->uniform_chunks = nw->uniform_chunks;
     return IPCFP_OK;  // nw (the old buffers) is released here
 }

@@ -165,56 +165,16 @@ int ipcfp_ctx_create(int device, ipcfp_ctx_t** out) {
         delete ctx;
         return IPCFP_E_NO_DEVICE;
     }
-    // K1 runs on a second stream beside the walk kernels (IPCFP_K1_STREAM: 0 = one stream, 1 = second stream
-    // [default], 2 = second stream with a CU mask, 3 = low-priority second stream).  The VALU-bound hash kernel
-    // and the latency-bound chain of walk kernels share the chip: measured on the 1M-receipt tipset the step
-    // drops 2.61 → 2.50 ms (the walk kernels lose ≈0.1 ms to K1, K1's 0.27 ms disappears from the critical
-    // path); CU masks and stream priorities add nothing over the plain second stream.  K1's results are
-    // complete after ipcfp_ctx_sync / ipcfp_witness_verify_cids, which wait for both streams.
-    // IPCFP_K1_STREAM=2: the second stream is confined to a share of the CUs (IPCFP_K1_CU_PERCENT, default 75;
-    // the mask sets bits in an even pattern so every shader engine / XCD keeps free CUs), so the walk
-    // kernels' chain of small launches always finds idle CUs while K1 grinds beside it.
+    // K1 runs on a second stream beside the walk kernels (IPCFP_K1_STREAM=0: on the main stream, which is also what a
+    // failed stream creation leaves).  The VALU-bound hash kernel and the latency-bound chain of walk kernels share the
+    // chip: measured on the 1M-receipt tipset the step drops 2.61 → 2.50 ms (the walk kernels lose ≈0.1 ms to K1, K1's
+    // 0.27 ms disappears from the critical path).  K1's results are complete after ipcfp_ctx_sync /
+    // ipcfp_witness_verify_cids, which wait for both streams.
     ctx->stream_k1 = ctx->stream;
     {
         const char* e = std::getenv("IPCFP_K1_STREAM");
-        const int mode = e ? std::atoi(e) : 1;
-        if (mode == 1 && hipStreamCreateWithFlags(&ctx->stream_k1, hipStreamNonBlocking) != hipSuccess)
+        if (!(e && std::atoi(e) == 0) && hipStreamCreateWithFlags(&ctx->stream_k1, hipStreamNonBlocking) != hipSuccess)
             ctx->stream_k1 = ctx->stream;
-        if (mode == 3) {
-            // K1 on the LOWEST-priority stream, the walk kernels on the highest: the dispatcher serves the chain
-            // of small latency-bound launches first and K1's wavefronts fill whatever is idle
-            int least = 0, greatest = 0;
-            hipStream_t hi = nullptr, lo = nullptr;
-            if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess &&
-                hipStreamCreateWithPriority(&hi, hipStreamNonBlocking, greatest) == hipSuccess &&
-                hipStreamCreateWithPriority(&lo, hipStreamNonBlocking, least) == hipSuccess) {
-                (void)hipStreamDestroy(ctx->stream);
-                ctx->stream = hi;
-                ctx->stream_k1 = lo;
-            } else {
-                if (hi) (void)hipStreamDestroy(hi);
-                ctx->stream_k1 = ctx->stream;
-            }
-        }
-        if (mode == 2) {
-            int pct = 75;
-            if (const char* f = std::getenv("IPCFP_K1_CU_PERCENT")) pct = std::atoi(f);
-            if (pct < 10) pct = 10;
-            if (pct > 100) pct = 100;
-            const int cus = ctx->props.multiProcessorCount > 0 ? ctx->props.multiProcessorCount : 256;
-            std::vector<uint32_t> mask(size_t((cus + 31) / 32), 0u);
-            // Bresenham spread of pct% ones over the CU bits
-            int acc = 0;
-            for (int i = 0; i < cus; ++i) {
-                acc += pct;
-                if (acc >= 100) {
-                    acc -= 100;
-                    mask[size_t(i) >> 5] |= 1u << (i & 31);
-                }
-            }
-            if (hipExtStreamCreateWithCUMask(&ctx->stream_k1, uint32_t(mask.size()), mask.data()) != hipSuccess)
-                ctx->stream_k1 = ctx->stream;
-        }
     }
     // the block-order event parse on a stream of its own (IPCFP_AUX_STREAM=0: on the main stream, in order)
     ctx->stream_aux = ctx->stream;
@@ -228,64 +188,9 @@ int ipcfp_ctx_create(int device, ipcfp_ctx_t** out) {
             ctx->aux_event = nullptr;
         }
     }
-    // IPCFP_RESERVE_CUS=r: r CUs of every XCD are kept for the narrow stream; K1's stream and the aux stream are re-made
-    // with the complementary mask.  (KFD hands the mask's bits out XCD by XCD — bit i belongs to XCD i % 8 — and inside
-    // an XCD shader engine by shader engine, so bits [0, 8r) are r CUs per XCD spread over its engines.  Whatever the
-    // mapping, the two masks are disjoint.)
-    if (const char* e = std::getenv("IPCFP_RESERVE_CUS")) {
-        const int cus = ctx->props.multiProcessorCount > 0 ? ctx->props.multiProcessorCount : 256;
-        const int r = std::atoi(e);
-        const int n_res = r * 8;
-        if (r > 0 && n_res < cus && ctx->stream_aux != ctx->stream && ctx->stream_k1 != ctx->stream) {
-            std::vector<uint32_t> keep(size_t((cus + 31) / 32), 0u), rest(size_t((cus + 31) / 32), 0u);
-            for (int i = 0; i < cus; ++i) (i < n_res ? keep : rest)[size_t(i) >> 5] |= 1u << (i & 31);
-            hipStream_t nar = nullptr, k1 = nullptr, aux = nullptr;
-            if (hipExtStreamCreateWithCUMask(&nar, uint32_t(keep.size()), keep.data()) == hipSuccess &&
-                hipExtStreamCreateWithCUMask(&k1, uint32_t(rest.size()), rest.data()) == hipSuccess &&
-                hipExtStreamCreateWithCUMask(&aux, uint32_t(rest.size()), rest.data()) == hipSuccess &&
-                hipEventCreateWithFlags(&ctx->narrow_event, hipEventDisableTiming) == hipSuccess) {
-                (void)hipStreamDestroy(ctx->stream_k1);
-                (void)hipStreamDestroy(ctx->stream_aux);
-                ctx->stream_k1 = k1;
-                ctx->stream_aux = aux;
-                ctx->stream_narrow = nar;
-            } else {
-                if (nar) (void)hipStreamDestroy(nar);
-                if (k1) (void)hipStreamDestroy(k1);
-                if (aux) (void)hipStreamDestroy(aux);
-            }
-        }
-    }
-    // the head stream (common.h stream_head); it needs the mailbox route's single-context verify call to be of any use
-    {
-        const char* e = std::getenv("IPCFP_HEAD_STREAM");
-        if (e && std::atoi(e) != 0 && !ctx->stream_narrow && ctx->stream_aux != ctx->stream) {  // measured: off (r03_experiments.md)
-            if (hipStreamCreateWithFlags(&ctx->stream_head, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&ctx->ctl_event, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&ctx->head_event, hipEventDisableTiming) != hipSuccess ||
-                hipEventRecord(ctx->ctl_event, ctx->stream) != hipSuccess) {
-                if (ctx->stream_head) (void)hipStreamDestroy(ctx->stream_head);
-                ctx->stream_head = nullptr;
-            }
-        }
-    }
-    if (const char* e = std::getenv("IPCFP_NARROW_MAX_WG")) ctx->narrow_max_wg = uint32_t(std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("IPCFP_K1_AFTER_BE")) ctx->k1_after_be = std::atoi(e) != 0;
-    if (const char* e = std::getenv("IPCFP_K1_DEFER")) ctx->k1_defer = std::atoi(e);
-    if (const char* e = std::getenv("IPCFP_K1_GATE")) ctx->k1_gate = std::atoi(e) != 0;
     if (const char* e = std::getenv("IPCFP_SPIN_SYNC")) ctx->spin_sync = std::atoi(e) != 0;
-    if (const char* e = std::getenv("IPCFP_HAMT_LEVELS")) ctx->hamt_levels = std::atoi(e);
-    if (const char* e = std::getenv("IPCFP_HAMT_TABLE")) ctx->hamt_table = std::atoi(e);
-    if (const char* e = std::getenv("IPCFP_HAMT_COOP")) ctx->hamt_coop = std::atoi(e);
-    if (const char* e = std::getenv("IPCFP_SCAN_FUSED")) ctx->scan_fused = std::atoi(e);
-    if (const char* e = std::getenv("IPCFP_FAST_VERIFY")) ctx->fast_verify = std::atoi(e);
     // wait_stream's polling event belongs to THIS device (created here, right after hipSetDevice(device))
     if (hipEventCreateWithFlags(&ctx->spin_event, hipEventDisableTiming) != hipSuccess) ctx->spin_event = nullptr;
-    if (const char* e = std::getenv("IPCFP_B2B_MODE")) ctx->b2b_mode = (std::atoi(e) >= 0 && std::atoi(e) <= 3) ? std::atoi(e) : 0;
-    if (const char* e = std::getenv("IPCFP_B2B_WG")) {
-        const int wg = std::atoi(e);
-        if (wg == 64 || wg == 128 || wg == 192 || wg == 256) ctx->b2b_wg = uint32_t(wg);
-    }
     if (hipHostMalloc(reinterpret_cast<void**>(&ctx->pinned), 64 * 1024, hipHostMallocDefault) == hipSuccess)
         ctx->pinned_cap = 64 * 1024;
     else
@@ -351,16 +256,11 @@ void ipcfp_ctx_destroy(ipcfp_ctx_t* ctx) {
     if (ctx->join_event) (void)hipEventDestroy(ctx->join_event);
     if (ctx->spin_event) (void)hipEventDestroy(ctx->spin_event);
     if (ctx->aux_event) (void)hipEventDestroy(ctx->aux_event);
+    if (ctx->outline_event) (void)hipEventDestroy(ctx->outline_event);
     if (ctx->stream_aux != ctx->stream) (void)hipStreamDestroy(ctx->stream_aux);
     if (ctx->stream_k1 != ctx->stream) (void)hipStreamDestroy(ctx->stream_k1);
     if (ctx->rehash_event) (void)hipEventDestroy(ctx->rehash_event);
-    if (ctx->stream_narrow) (void)hipStreamDestroy(ctx->stream_narrow);
     if (ctx->stream_copy) (void)hipStreamDestroy(ctx->stream_copy);
-    if (ctx->stream_head) (void)hipStreamDestroy(ctx->stream_head);
-    if (ctx->ctl_event) (void)hipEventDestroy(ctx->ctl_event);
-    if (ctx->head_event) (void)hipEventDestroy(ctx->head_event);
-    if (ctx->narrow_event) (void)hipEventDestroy(ctx->narrow_event);
-    if (ctx->k1_gate_event) (void)hipEventDestroy(ctx->k1_gate_event);
     (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -377,7 +277,6 @@ int ipcfp_ctx_set_tuning(ipcfp_ctx_t* ctx, const char* key, int64_t value) {
     if (k == "hamt_levels") ctx->hamt_levels = int(value);
     else if (k == "hamt_table") ctx->hamt_table = int(value);
     else if (k == "hamt_coop") ctx->hamt_coop = int(value);
-    else if (k == "scan_fused") ctx->scan_fused = int(value);
     else if (k == "fast_verify") ctx->fast_verify = int(value);
     else return set_error(ctx, IPCFP_E_INVALID, "unknown tuning key '%s'", key);
     return IPCFP_OK;
@@ -386,7 +285,6 @@ int ipcfp_ctx_set_tuning(ipcfp_ctx_t* ctx, const char* key, int64_t value) {
 int ipcfp_ctx_sync(ipcfp_ctx_t* ctx) {
     if (!ctx) return IPCFP_E_INVALID;
     IPCFP_HIP(ctx, hipSetDevice(ctx->device));  // (a multi-device process: the event record below is per device)
-    if (int rc = ipcfp::k1_flush(ctx)) return rc;
     IPCFP_HIP(ctx, wait_stream(ctx, ctx->stream));
     IPCFP_HIP(ctx, wait_stream(ctx, ctx->stream_k1));
     if (ctx->stream_aux != ctx->stream) IPCFP_HIP(ctx, wait_stream(ctx, ctx->stream_aux));

@@ -43,8 +43,8 @@ static hipError_t grow(void*& p, size_t& cap, size_t need) {
 
 // K7 for a batch.  Default for a batch of ≥ 1024 queries: LEVEL BY LEVEL (kernels/hamt_levels.hip) — every node the batch
 // visits is decoded once, a query is SHA-256 + one record per level — with the per-query walker (k_hamt_get) behind it
-// for whatever that leaves pending.  IPCFP_HAMT_LEVELS=0: the walker alone (round 3's path; small batches take it
-// anyway).  IPCFP_HAMT_TABLE=1 (A/B measurements): tabulate EVERY block of the witness first (kernels/hamt_table.h).
+// for whatever that leaves pending.  Tuning key hamt_levels = 0: the walker alone (round 3's path; small batches take it
+// anyway).  Tuning key hamt_table = 1 (A/B measurements): tabulate EVERY block of the witness first (kernels/hamt_table.h).
 int hamt_get_batch(ipcfp_ctx* ctx, ipcfp_witness* w, const CidKey& root, uint32_t bit_width, int vkind, const uint8_t* keys_d,
                    const uint32_t* key_off_d, const uint32_t* key_len_d, uint32_t n, uint8_t* status_d, void* loc_d) {
     const int forced_table = ctx->hamt_table, levels_mode = ctx->hamt_levels;

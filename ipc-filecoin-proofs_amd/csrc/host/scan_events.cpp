@@ -229,7 +229,7 @@ int scan_events_device(ipcfp_ctx* ctx, ipcfp_witness* w, const CidKey& root, con
         if (rc) return rc;
     }
     // ---- the tail in ONE launch, results through the mailbox: no read-back copy, no stream synchronisation ----
-    if (ctx->scan_fused != 0 && ctx->mailbox && tview.receipts && !touched_d && n && cap_matches <= (1ull << 26)) {
+    if (ctx->mailbox && tview.receipts && !touched_d && n && cap_matches <= (1ull << 26)) {
         unsigned long long* tail_scratch = nullptr;
         rc = scan_tail_scratch(ctx, div_up(n, 1024), &tail_scratch);
         if (rc) return rc;

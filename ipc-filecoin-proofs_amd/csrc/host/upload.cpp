@@ -62,13 +62,17 @@ static UploadRing* ring_of(ipcfp_ctx* ctx) {
     return r;
 }
 
+bool upload_ring_mode() {
+    static const bool ring = [] {
+        const char* e = std::getenv("IPCFP_UPLOAD_MODE");
+        return e && std::atoi(e) != 0;
+    }();
+    return ring;
+}
+
 int upload(ipcfp_ctx* ctx, void* dst_d, const void* src, size_t bytes, hipStream_t s) {
     if (bytes == 0) return IPCFP_OK;
-    static const int mode = [] {
-        const char* e = std::getenv("IPCFP_UPLOAD_MODE");
-        return e ? std::atoi(e) : 0;
-    }();
-    if (bytes >= 2 * kChunk && mode == 0) {  // the runtime's blocking copy: nothing queued on `s` may still use dst
+    if (bytes >= 2 * kChunk && !upload_ring_mode()) {  // the runtime's blocking copy: nothing queued on `s` may still use dst
         IPCFP_HIP(ctx, hipStreamSynchronize(s));
         IPCFP_HIP(ctx, hipMemcpy(dst_d, src, bytes, hipMemcpyHostToDevice));
         return IPCFP_OK;

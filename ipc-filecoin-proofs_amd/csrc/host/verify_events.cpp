@@ -5,7 +5,6 @@
 // device (header facts + execution order — both recomputed PER PROOF by the reference,
 // events/verifier.rs:105,115,190), then verify the whole batch with one kernel.
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -104,7 +103,6 @@ int verify_packed(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& t
         int rc_fast = verify_packed_fast(ctx, w, tcs, claims_d, n, blob_d, blob_len, trust, filter, status_d, where_d, &done, ride);
         if (rc_fast) return rc_fast;
         if (done) return IPCFP_OK;
-        if (int rc_k1 = k1_flush(ctx)) return rc_k1;  // (a noted K1 launch the fast route did not get to queue)
         tcs = saved;
     }
     const WitnessView view = witness_view(w);
@@ -489,11 +487,7 @@ int ipcfp_verify_event_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipcfp_
     // execution order, none of which reads a claim; launch_verify_events' callers wait for the copy (upload_task_wait).
     // (IPCFP_UPLOAD_MODE=1, or a batch too small to matter: uploaded here, first)
     int rc = IPCFP_OK;
-    static const bool beside = [] {
-        const char* e = std::getenv("IPCFP_UPLOAD_MODE");
-        return !(e && std::atoi(e) != 0);
-    }();
-    if (beside && n * sizeof(EventClaimPacked) >= (size_t(8) << 20)) {
+    if (!upload_ring_mode() && n * sizeof(EventClaimPacked) >= (size_t(8) << 20)) {
         IPCFP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (nothing queued earlier may still use the buffers just taken)
         ctx->upload_task = upload_task_start(ctx, cd.p, claims, n * sizeof(EventClaimPacked), bd.p, blob, blob_len);
     }
@@ -658,12 +652,8 @@ int ipcfp_verify_event_claims_range(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const 
             return set_error(ctx, IPCFP_E_INVALID, "the claim batch is not in exec_index order (ipcfp_route_event_claims takes any order)");
         return IPCFP_OK;
     };
-    static const bool allow_guess = [] {
-        const char* e = std::getenv("IPCFP_CLAIMS_WINDOW_GUESS");
-        return !(e && std::atoi(e) == 0);
-    }();
     bool missed = false;
-    if (allow_guess && m * sizeof(EventClaimPacked) >= (size_t(1) << 20)) {  // (below: a thread and a join cost what the synchronisation does)
+    if (m * sizeof(EventClaimPacked) >= (size_t(1) << 20)) {  // (below: a thread and a join cost what the synchronisation does)
         const int rc = attempt(true, &missed);
         if (rc || !missed) return rc;
     }

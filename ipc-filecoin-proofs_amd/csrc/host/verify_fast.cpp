@@ -15,7 +15,6 @@
 // The call synchronises once.  Same kernels otherwise, same results: tests/test_gpu_events.py, test_gpu_baseline_sizes.py,
 // test_gpu_enum_shapes.py (every shape that leaves the dense path) run through this file first.
 #include <chrono>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -62,7 +61,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
                                     uint32_t n, const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust,
                                     const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d, bool* done, ScanRide* ride) {
     static const ipcfp_trust_policy_t accept_all = {0, 0, 0, 0};
-    const bool enabled = ctx->fast_verify != 0;  // (env IPCFP_FAST_VERIFY / ipcfp_ctx_set_tuning "fast_verify")
+    const bool enabled = ctx->fast_verify != 0;  // (ipcfp_ctx_set_tuning "fast_verify")
     *done = false;
     if (!enabled || !ctx->mailbox || tcs.size() != 1 || !w->use_event_table || ctx->stream_aux == ctx->stream) return IPCFP_OK;
     const TipsetCtxDev& in = tcs[0];
@@ -75,33 +74,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     int rc = ctx->has_scan_hint ? block_table_prefetch(ctx, w, &ctx->scan_hint.filter, int(ctx->scan_hint.has_actor), ctx->scan_hint.actor)
                                 : block_table_prefetch(ctx, w, nullptr, 0, 0);
     if (rc) return rc;
-    // Where the head of the call is queued.  `ctx->stream` IS that stream until the hand-back, so every helper that queues
-    // "on the call's stream" (control words, small copies, the launchers) follows without knowing.
-    //   * head stream (IPCFP_HEAD_STREAM=1, measured and off): the tipset prologue runs BESIDE the CID index's inserts — it waits for the point where
-    //     the table was cleared, not for the inserts behind it, and its lookups wait for their keys (tipset_prepare.hip
-    //     LiveIndex); the main stream takes over with k_enum_roots.  Not when a block may exceed the prologue's LDS stage
-    //     (the general companion wants the finished index).
-    //   * narrow stream (IPCFP_RESERVE_CUS, measured and off): prologue, roots and the narrow interior levels on reserved
-    //     CUs, behind the inserts; launch_dense_walk hands back.
-    struct StreamSwap {
-        ipcfp_ctx* c;
-        hipStream_t saved;
-        ~StreamSwap() {
-            if (c->stream != saved) (void)hipStreamSynchronize(c->stream);  // (left early: nothing handed the work over)
-            c->stream = saved;
-        }
-    } swap{ctx, ctx->stream};
     const bool need_general = uint64_t(w->max_block_len) + 32u > uint64_t(kPrologueStageChunks) * 16u;
-    const bool head = ctx->stream_head && w->index_event && w->index_done.p && !need_general;
-    if (head) {
-        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_head, w->index_event, 0));  // the witness is in place, the table cleared
-        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_head, ctx->ctl_event, 0));  // the control block re-initialised
-        ctx->stream = ctx->stream_head;
-    } else if (ctx->stream_narrow) {
-        IPCFP_HIP(ctx, hipEventRecord(ctx->narrow_event, ctx->stream));  // behind the index build (and the preprimed control block)
-        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_narrow, ctx->narrow_event, 0));
-        ctx->stream = ctx->stream_narrow;
-    }
     // The context on the device: a slice of the control block's ZERO half when there is room (re-initialised at the end of
     // the previous call) — its inputs then travel as a kernel argument of the prologue, which writes them in; no copy
     // kernel at the head of the call (17.7 µs beside the side streams' grids: profiles/r03_last_commit_timeline.txt).
@@ -111,9 +84,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     } tcs_d;
     TipsetInputs inputs;
     std::memcpy(&inputs, &tcs[0], sizeof inputs);
-    const bool head_or_general = (ctx->stream_head && w->index_event && w->index_done.p) ||
-                                 uint64_t(w->max_block_len) + 32u > uint64_t(kPrologueStageChunks) * 16u;
-    tcs_d.p = head_or_general ? nullptr : static_cast<TipsetCtxDev*>(ctl_take(ctx, sizeof(TipsetCtxDev), false));
+    tcs_d.p = need_general ? nullptr : static_cast<TipsetCtxDev*>(ctl_take(ctx, sizeof(TipsetCtxDev), false));
     const bool inline_inputs = tcs_d.p != nullptr;
     if (!inline_inputs) {
         IPCFP_HIP(ctx, tcs_d.own.alloc(1));
@@ -130,7 +101,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     DevBuf<DenseNode> dense_frontier;
     DevBuf<uint32_t> small_own;
     DevBuf<uint64_t> info_own;
-    uint32_t* small = nullptr;  // [0] = max height (unused here), [2] = anomaly flag (the dense walk, the live lookups)
+    uint32_t* small = nullptr;  // [0] = max height (unused here), [2] = anomaly flag (the dense walk)
     uint64_t* info_d = nullptr;
     IPCFP_HIP(ctx, frontier.alloc(n_all));
     IPCFP_HIP(ctx, dense_frontier.alloc(n_all));
@@ -141,18 +112,8 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     // left to a launch of their own on the aux stream, joined at the end of the call; not when a block may need the
     // general companion, which hashes inline)
     const bool defer_rehash = !need_general && ctx->rehash_event != nullptr;
-    rc = head ? launch_tipset_prepare(ctx, view, &job, nullptr, 1, false, w->index_done.p, w->index_wgs, small + 2, defer_rehash)
-              : launch_tipset_prepare(ctx, view, &job, nullptr, 1, need_general, nullptr, 0, nullptr, defer_rehash,
-                                      inline_inputs ? &inputs : nullptr);
+    rc = launch_tipset_prepare(ctx, view, &job, nullptr, 1, need_general, defer_rehash, inline_inputs ? &inputs : nullptr);
     if (rc) return rc;
-    if (head) {  // hand back: the main stream (behind the inserts by its own order) waits for the prologue
-        IPCFP_HIP(ctx, hipEventRecord(ctx->head_event, ctx->stream));
-        IPCFP_HIP(ctx, hipStreamWaitEvent(swap.saved, ctx->head_event, 0));
-        ctx->stream = swap.saved;
-        for (auto& r : ctx->pending)
-            if (r.stream == ctx->stream_head) r.stream = ctx->stream;
-        if (prof) prof->stream = ctx->stream;
-    }
     // ---- the roots; their shapes come back through the mailbox ----
     const unsigned long long seq = ++ctx->mailbox_seq;
     rc = launch_enum_roots(ctx, view, ex.roots.p, n_all, VK_CID, frontier.p, small, ex.err.p, info_d, ctx->mailbox_dev, seq,
@@ -218,15 +179,9 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     // the receipt leaves (and their records) are consumed on the aux stream, the message keys on the main stream: the two
     // leaf kernels fork accordingly and run side by side
     rc = launch_dense_walk(ctx, view, dense_frontier.p, plan, a.p, b.p, nullptr, ex.keys.p, rleaves.p, small + 2, ctx->stream_aux,
-                           ctx->main_event, ctx->stream != swap.saved ? swap.saved : nullptr, ctx->narrow_event, ctx->narrow_max_wg,
-                           &clear, &recs);
+                           ctx->main_event, &clear, &recs);
     if (rc) return rc;
-    // (the main stream now waits for everything the narrow stream was given: its small copies are the main stream's)
-    for (auto& r : ctx->pending)
-        if (ctx->stream_narrow && r.stream == ctx->stream_narrow) r.stream = ctx->stream;
-    if (prof) prof->stream = ctx->stream;  // (started on the narrow stream, ends on the main one)
     prof.reset();
-    if (ctx->k1_defer == 1 && (rc = k1_flush(ctx, true))) return rc;
     // the receipts the table does not cover: the general walker, aux stream, right behind the leaves
     rc = launch_receipt_walk(ctx, view, rleaves.p, n_rcpt, table->has_counts ? &w->bt_filter.filter : nullptr,
                              int(w->bt_filter.has_actor), w->bt_filter.actor, table->receipts.p,
@@ -239,7 +194,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     DevBuf<uint32_t> ride_counts, ride_offsets;
     DevBuf<unsigned long long> ride_err_own;
     unsigned long long ride_seq = 0;
-    if (ride && ctx->scan_fused != 0 && ride->cap_matches <= (1ull << 26) && (!ride->has_d || ride->cap_receipts >= n_rcpt)) {
+    if (ride && ride->cap_matches <= (1ull << 26) && (!ride->has_d || ride->cap_receipts >= n_rcpt)) {
         struct OnAux {  // everything queued "on the call's stream" below goes to the aux stream
             ipcfp_ctx* c;
             hipStream_t saved;
@@ -304,12 +259,10 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     prof.reset();
     rc = event_table_join(ctx, w);  // (the receipt records: aux_event as recorded behind k_receipt_walk)
     if (rc) return rc;
-    if (ctx->k1_defer == 2 && (rc = k1_flush(ctx, true))) return rc;
     if ((rc = claims_ready(ctx))) return rc;  // claims that were crossing PCIe beside all of the above are in HBM
     rc = launch_verify_events(ctx, view, claims_d, n, tcs_d.p, 1, blob_d, blob_len, trust ? *trust : accept_all, filter, status_d,
                               where_d, /*tabulated=*/true);
     if (rc) return rc;
-    if ((rc = k1_flush(ctx, true))) return rc;  // (mode 3, and whatever is still noted)
     // the aux stream's tail — the re-hash, the riding scan — joins before the flags are read: its errors and the scan's
     // results are in when the call's one synchronisation returns.  (Recorded only now: the join above took the earlier
     // record, so the verify kernel does not wait for these.)

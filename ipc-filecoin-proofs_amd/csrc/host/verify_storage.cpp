@@ -3,7 +3,6 @@
 // Host side of src/proofs/storage/verifier.rs:24-63: parse the claim strings once
 // (parse_cid → src/proofs/common/witness.rs:60-64; hex → storage/verifier.rs:155-157), upload the
 // packed claims, run one kernel over the batch, download the status bytes.
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -45,7 +44,7 @@ static const ipcfp_trust_policy_t kAcceptAll = {0, 0, 0, 0};
 //      proof that passes through it — a contract's storage root is decoded once, not 256 times),
 //   3. settles every claim from its run's record and two or three table records (k_verify_storage_table),
 // and the one-lane kernel takes what that leaves pending (an inline small-map layout, a block the table does not cover).
-// A small batch — and everything, with IPCFP_HAMT_TABLE=0 — goes through the one-lane kernel alone.  The table lives
+// A small batch — and everything, with the tuning key hamt_table = 0 — goes through the one-lane kernel alone.  The table lives
 // for this call only.  One host synchronisation (the number of runs).
 //
 // The COLUMN form (`cols`: include/ipcfp.h "storage claims in run-compressed, column form") takes the same steps with the
@@ -59,7 +58,7 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
     if (n == 0) return IPCFP_OK;
     ProfileScope prof(ctx, IPCFP_K_STORAGE_VERIFY);
     const WitnessView w = witness_view(wit);
-    const int forced = ctx->hamt_table;  // (env IPCFP_HAMT_TABLE / ipcfp_ctx_set_tuning "hamt_table")
+    const int forced = ctx->hamt_table;  // (ipcfp_ctx_set_tuning "hamt_table")
     const bool tabled = forced == 1 || (forced != 0 && uint64_t(n) * 16u >= wit->n);
     ColumnClaimSrc csrc{};
     if (cols) csrc = ColumnClaimSrc{static_cast<const StorageRunRec*>(cols->runs), cols->slot, cols->value, cols->cflags};
@@ -83,91 +82,44 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
         return launch_verify_storage_lanes(ctx, w, csrc, run_of.p, n, trust, status_d, 0);
     }
     constexpr uint32_t kUndecided = 0xfdu;
+    constexpr uint32_t kTableKinds = HK_ACTOR_STATE | HK_VEC_U8;
     DevBuf<HamtNodeRec> table;
     DevBuf<uint32_t> long_list, long_count;
     IPCFP_HIP(ctx, table.alloc(wit->n));
-    static const bool ring = [] { const char* e = std::getenv("IPCFP_HAMT_TABLE_FORM"); return e && e[0] == 'r'; }();
-    // Round 6: the node table (0.6 ms of one-lane parses, latency-bound) and the runs' boundary pass (0.18 ms of streaming
-    // 248-byte records, bandwidth-bound) need nothing of each other: the table goes to the AUX stream, its 32-lane outline
-    // of the long blocks — whose grid wants the list's size, i.e. the call's one synchronisation — to the K1 stream beside it,
-    // and the main stream runs flags → scan → heads → typed decodes meanwhile and joins both before the first kernel that
-    // reads a record.  IPCFP_STORAGE_SIDE=0: everything on the main stream in round 5's order.
-    static const bool side_env = [] { const char* e = std::getenv("IPCFP_STORAGE_SIDE"); return !(e && std::atoi(e) == 0); }();
-    const bool side = side_env && !ring && ctx->stream_aux != ctx->stream && ctx->aux_event && ctx->main_event;
+    // The node table (0.6 ms of one-lane parses, latency-bound) and the runs' boundary pass (0.18 ms of streaming 248-byte
+    // records, bandwidth-bound) need nothing of each other: the table goes to the AUX stream, its 32-lane outline of the
+    // long blocks — whose grid wants the list's size, i.e. the call's one synchronisation — to the K1 stream beside it, and
+    // the main stream runs flags → scan → heads → typed decodes meanwhile and joins both before the first kernel that reads
+    // a record.  A context without an aux stream of its own (IPCFP_AUX_STREAM=0) queues everything on the main stream, in order.
+    const bool side = ctx->stream_aux != ctx->stream && ctx->aux_event && ctx->main_event;
     const bool side2 = side && ctx->stream_k1 != ctx->stream && ctx->stream_k1 != ctx->stream_aux;
     // (declared AFTER table / long_list / long_count: an early return drains the side streams before those buffers go back
-    // to the pool — ADVICE r5)
+    // to the pool)
     StreamDrainGuard aux_guard(ctx->stream_aux), k1_guard(ctx->stream_k1);
-    int rc = IPCFP_OK;
-    static const uint32_t table_kinds = [] {  // IPCFP_TABLE_FAST=0: the node table reads every entry item by item (round 5's way)
-        const char* e = std::getenv("IPCFP_TABLE_FAST");
-        return HK_ACTOR_STATE | HK_VEC_U8 | (e && std::atoi(e) == 0 ? uint32_t(HK_ITEM_BY_ITEM) : 0u);
-    }();
-    // (IPCFP_STORAGE_EARLY_OUTLINE=1, measured and left off: see below)
-    static const bool early_env = [] { const char* e = std::getenv("IPCFP_STORAGE_EARLY_OUTLINE"); return e && std::atoi(e) == 1; }();
-    const bool early_outline = side2 && early_env;
-    uint32_t n_long = 0;
-    hipEvent_t outline_event = nullptr;
-    // the outline of the long blocks (its grid is the list's size): beside the lane kernel when that runs on the aux stream,
-    // else on the aux stream beside the runs' typed decodes (round 5)
-    auto queue_outline = [&]() -> int {
-        if (!n_long) return IPCFP_OK;
-        hipStream_t s = ctx->stream;
-        if (side2) {
-            s = ctx->stream_k1;
-            k1_guard.armed = true;
-            IPCFP_HIP(ctx, hipStreamWaitEvent(s, ctx->main_event, 0));
-        } else if (ctx->stream_aux != ctx->stream && ctx->aux_event) {
-            s = ctx->stream_aux;
-            aux_guard.armed = true;
-        }
-        int rc2 = launch_hamt_outline_list(ctx, s, w, table.p, long_list.p, long_count.p, n_long);
-        if (!rc2) rc2 = launch_hamt_node_table_rest(ctx, s, w, long_list.p, long_count.p, n_long, HK_ACTOR_STATE | HK_VEC_U8, table.p);
-        if (rc2) return rc2;
-        if (s == ctx->stream_k1) {
-            if (!ctx->k1_gate_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&ctx->k1_gate_event, hipEventDisableTiming));
-            outline_event = ctx->k1_gate_event;
-            IPCFP_HIP(ctx, hipEventRecord(outline_event, s));
-        }
-        return IPCFP_OK;
-    };
-    if (ring) {  // (round 3's form, for A/B runs: eight lanes per block with the ring reader, every block)
-        rc = launch_hamt_node_table(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), table_kinds, table.p);
+    // the long blocks (4-5 KB state-tree nodes: the head of the schedule) as a work list for the 32-lane outline …
+    IPCFP_HIP(ctx, long_list.alloc(wit->n));
+    IPCFP_HIP(ctx, long_count.alloc(1));
+    IPCFP_HIP(ctx, hipMemsetAsync(long_count.p, 0, 4, ctx->stream));
+    int rc = launch_hamt_list_long(ctx, wit->k1_meta.p, uint32_t(wit->n), long_list.p, long_count.p);
+    if (rc) return rc;
+    // … everything shorter: one block per lane, line-staged reader
+    if (side) {
+        IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));  // (everything that made the witness and took `table` from the pool is behind this)
+        IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
+        aux_guard.armed = true;
+        hipStream_t saved = ctx->stream;
+        ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
+        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kTableKinds, table.p);
+        ctx->stream = saved;
     } else {
-        // the long blocks (4-5 KB state-tree nodes: the head of the schedule) as a work list for the 32-lane outline …
-        IPCFP_HIP(ctx, long_list.alloc(wit->n));
-        IPCFP_HIP(ctx, long_count.alloc(1));
-        IPCFP_HIP(ctx, hipMemsetAsync(long_count.p, 0, 4, ctx->stream));
-        rc = launch_hamt_list_long(ctx, wit->k1_meta.p, uint32_t(wit->n), long_list.p, long_count.p);
-        if (!rc && early_outline) {
-            // The outline's grid wants the list's size.  Read behind the runs' boundary pass (the call's one synchronisation) it
-            // starts 0.33 ms into the call and ends with the lane kernel; read HERE — a second synchronisation, of a stream
-            // that holds 7 µs of work — it starts with the call.  Measured: 1.40 ms against 1.21 (profiles/r06_experiments.md) —
-            // the synchronisation puts 60 µs in front of everything and the lane kernel, which the call waits for, shares the
-            // chip with the outline from its first workgroup (546 -> 694 µs).  Off.
-            IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
-            IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
-            IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));
-            rc = queue_outline();
-        }
-        // … everything shorter: one block per lane, line-staged reader
-        if (!rc && side) {
-            IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));  // (everything that made the witness and took `table` from the pool is behind this)
-            IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
-            aux_guard.armed = true;
-            hipStream_t saved = ctx->stream;
-            ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
-            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), table_kinds, table.p);
-            ctx->stream = saved;
-        } else if (!rc) {
-            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), table_kinds, table.p);
-        }
+        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kTableKinds, table.p);
     }
     if (rc) return rc;
     if (wait_upload) {  // (the node table is on its way: from here on the kernels read claims)
         rc = upload_task_wait(ctx);
         if (rc) return rc;
     }
+    // the runs: the row form finds them (flags → scan → heads), the column form brings them and has them checked
     DevBuf<uint32_t> flag, pos;
     DevBuf<uint64_t> scratch, total_d;
     DevBuf<StorageRun> runs;
@@ -190,12 +142,32 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
         if (rc) return rc;
         IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
     }
-    if (!ring && !early_outline) IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
+    // the call's one synchronisation: the number of runs and of long blocks
+    uint32_t n_long = 0;
+    IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
     IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
     if (bad) return set_error(ctx, IPCFP_E_INVALID, "the run table does not tile the %u claims", n);  // (the guards drain the side streams)
-    if (!early_outline) {
-        rc = queue_outline();
+    // the outline of the long blocks (its grid is the list's size): on the K1 stream beside the lane kernel when that runs on
+    // the aux stream, else on the aux stream beside the runs' typed decodes, else in order
+    hipEvent_t outline_done = nullptr;
+    if (n_long) {
+        hipStream_t s = ctx->stream;
+        if (side2) {
+            s = ctx->stream_k1;
+            k1_guard.armed = true;
+            IPCFP_HIP(ctx, hipStreamWaitEvent(s, ctx->main_event, 0));
+        } else if (ctx->stream_aux != ctx->stream && ctx->aux_event) {
+            s = ctx->stream_aux;
+            aux_guard.armed = true;
+        }
+        rc = launch_hamt_outline_list(ctx, s, w, table.p, long_list.p, long_count.p, n_long);
+        if (!rc) rc = launch_hamt_node_table_rest(ctx, s, w, long_list.p, long_count.p, n_long, kTableKinds, table.p);
         if (rc) return rc;
+        if (s == ctx->stream_k1) {
+            if (!ctx->outline_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&ctx->outline_event, hipEventDisableTiming));
+            outline_done = ctx->outline_event;
+            IPCFP_HIP(ctx, hipEventRecord(outline_done, s));
+        }
     }
     if (aux_guard.armed) IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
     if (!cols) {
@@ -207,7 +179,7 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
     if (rc) return rc;
     // the table is whole from here on
     if (aux_guard.armed) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_event, 0));
-    if (outline_event) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_event, 0));
+    if (outline_done) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_done, 0));
     aux_guard.armed = k1_guard.armed = false;  // the main stream is ordered behind the side kernels now: pool reuse on it is safe
     rc = cols ? launch_storage_run_actors_table(ctx, w, table.p, csrc, runs.p, uint32_t(n_runs), kUndecided)
               : launch_storage_run_actors_table(ctx, w, table.p, claims_d, runs.p, uint32_t(n_runs), kUndecided);
@@ -215,22 +187,15 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
     rc = cols ? launch_storage_run_actors_lane(ctx, w, csrc, runs.p, uint32_t(n_runs), kUndecided)
               : launch_storage_run_actors_lane(ctx, w, claims_d, runs.p, uint32_t(n_runs), kUndecided);
     if (rc) return rc;
-    // the first step of the runs' storage gets, once per run (IPCFP_STORAGE_RUN_CHILDREN=0: every claim by itself)
-    static const bool run_children = [] { const char* e = std::getenv("IPCFP_STORAGE_RUN_CHILDREN"); return !(e && std::atoi(e) == 0); }();
+    // the first step of the runs' storage gets, once per run; then every claim from its run's record and the table, and the
+    // one-lane kernel for what that leaves pending
     DevBuf<uint32_t> root_children;
-    // (the column form's claims have no CID to compare with: their run's word is made whatever the switch says, which then only
-    // decides who takes the first step of a get)
-    if ((run_children || cols) && n_runs) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 34u));
-    if (cols) {
-        rc = launch_verify_storage_table(ctx, w, table.p, csrc, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, run_children, trust,
-                                         kUndecided, status_d);
-        if (rc) return rc;
-        return launch_verify_storage_lanes(ctx, w, csrc, run_of.p, n, trust, status_d, 1);
-    }
-    rc = launch_verify_storage_table(ctx, w, table.p, claims_d, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, trust, kUndecided,
-                                     status_d);
+    if (n_runs) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 34u));
+    rc = cols ? launch_verify_storage_table(ctx, w, table.p, csrc, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, trust, kUndecided, status_d)
+              : launch_verify_storage_table(ctx, w, table.p, claims_d, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p, trust, kUndecided, status_d);
     if (rc) return rc;
-    return launch_verify_storage_lanes(ctx, w, claims_d, n, trust, status_d, 1);
+    return cols ? launch_verify_storage_lanes(ctx, w, csrc, run_of.p, n, trust, status_d, 1)
+                : launch_verify_storage_lanes(ctx, w, claims_d, n, trust, status_d, 1);
     // (the scratch buffers go back to the pool on return; reuse is ordered on the one stream)
 }
 

@@ -103,10 +103,6 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
                       DenseNode* a, DenseNode* b, LeafRef* leaves_main, CidKey* keys_main, LeafRef* leaves_extra, uint32_t* anomaly_d,
                       hipStream_t leaves_stream = nullptr,  // non-null (with fork_event): k_dense_leaves runs there, beside
                       hipEvent_t fork_event = nullptr,      // k_dense_link_leaves on the main stream
-                      // non-null: the caller runs on the narrow stream (ctx->stream is that stream); the first level of more
-                      // than `narrow_max_wg` workgroups — the leaves at the latest — hands over to `wide_stream` through
-                      // `wide_event`, and ctx->stream is `wide_stream` on return
-                      hipStream_t wide_stream = nullptr, hipEvent_t wide_event = nullptr, uint32_t narrow_max_wg = 0,
                       const DenseClear* clear = nullptr,
                       // non-null: the extra root's leaves take k_dense_receipt_leaves (a receipts tree), on the leaves' stream
                       const DenseReceiptOut* receipts = nullptr);

@@ -3,7 +3,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -12,6 +11,7 @@
 #include "event_table.h"
 #include "launch.h"
 #include "tipset_ctx.h"
+#include "txmeta_dev.h"
 
 namespace ipcfp {
 
@@ -74,7 +74,7 @@ __device__ __forceinline__ void txmeta_rehash_lane(const WitnessView& w, const T
         enum_error(err, seq, 0, IPCFP_ST_ERR_DECODE);
         return;
     }
-    uint64_t d[4];
+    CidKey re;
     if (w.len[tb] == 87u && o[0] == 6u && l[0] == 38u && o[1] == 49u && l[1] == 38u) {
         // `82 | d8 2a 58 27 00 ‖ 38 | d8 2a 58 27 00 ‖ 38`: the canonical re-encoding IS the block — one compression
         // straight from its bytes (blocks sit on 128-byte lines with tail slack), no byte buffer in scratch
@@ -89,32 +89,11 @@ __device__ __forceinline__ void txmeta_rehash_lane(const WitnessView& w, const T
         b2b::mask_tail(m, 87u);
         uint64_t h[8];
         b2b::init256(h);
-        b2b::compress<0>(h, m, 87ull, true);
-        d[0] = h[0];
-        d[1] = h[1];
-        d[2] = h[2];
-        d[3] = h[3];
+        b2b::compress(h, m, 87ull, true);
+        txmeta_cid_of_digest(h, re);
     } else {
-    uint8_t enc[200];
-    uint32_t n = 0;
-    enc[n++] = 0x82;
-    for (int k = 0; k < 2; ++k) {
-        enc[n++] = 0xd8;
-        enc[n++] = 0x2a;
-        const uint32_t bl = l[k] + 1;
-        if (bl < 24) enc[n++] = uint8_t(0x40 | bl);
-        else { enc[n++] = 0x58; enc[n++] = uint8_t(bl); }
-        enc[n++] = 0x00;
-        for (uint32_t i = 0; i < l[k]; ++i) enc[n++] = uint8_t(r.at(o[k] + i));
+        txmeta_rehash(r, o[0], l[0], o[1], l[1], re);
     }
-    blake2b256_small(enc, n, d);
-    }
-    CidKey re;
-    re.w[0] = 0x00002002e4a07101ULL | (d[0] << 48);
-    re.w[1] = (d[0] >> 16) | (d[1] << 48);
-    re.w[2] = (d[1] >> 16) | (d[2] << 48);
-    re.w[3] = (d[2] >> 16) | (d[3] << 48);
-    re.w[4] = d[3] >> 16;
     if (!cid_equal(re, load_cid_slot(w.cids, tb))) enum_error(err, seq, 0, IPCFP_ST_ERR_TXMETA_MISMATCH);
 }
 
@@ -1052,30 +1031,18 @@ void dense_plan(const std::vector<uint64_t>& root_info, uint32_t n_roots, int vk
 // (k_enum_roots); a / b: two frontier buffers of plan.biggest entries.  The root shapes travel as a kernel argument.
 int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* frontier, const DensePlan& plan,
                       DenseNode* a, DenseNode* b, LeafRef* leaves_main, CidKey* keys_main, LeafRef* leaves_extra, uint32_t* anomaly_d,
-                      hipStream_t leaves_stream, hipEvent_t fork_event, hipStream_t wide_stream, hipEvent_t wide_event,
-                      uint32_t narrow_max_wg, const DenseClear* clear, const DenseReceiptOut* receipts) {
+                      hipStream_t leaves_stream, hipEvent_t fork_event, const DenseClear* clear, const DenseReceiptOut* receipts) {
     const DenseNode* src = frontier;
-    auto widen = [&]() -> hipError_t {  // the narrow stream's part ends here
-        if (!wide_stream || ctx->stream == wide_stream) return hipSuccess;
-        hipError_t e = hipEventRecord(wide_event, ctx->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(wide_stream, wide_event, 0);
-        ctx->stream = wide_stream;
-        return e;
-    };
     // (All interior levels as ONE persistent launch — a workgroup per CU, a grid barrier per level — was built and is
     // slower: 382 µs against 238 µs for the six launches.  What stretches a level beside K1 and the event parse is the
     // latency of its three dependent loads under their memory traffic, not the dispatch; a barrier adds an L2
     // write-back and an L1 invalidate per level on top.  profiles/r03_experiments.md)
     uint32_t level_from = plan.max_height;
     unsigned long long* set_err = receipts ? receipts->err : nullptr;  // (taken by the first interior launch)
-    {   // the narrow levels at the top: one launch (k_dense_top).  IPCFP_DENSE_TOP = the widest level it takes (0: none)
-        static const uint32_t top_max = [] {
-            const char* e = std::getenv("IPCFP_DENSE_TOP");
-            return e ? uint32_t(std::atoi(e)) : kDenseTopMax;
-        }();
+    {   // the narrow levels at the top (at most kDenseTopMax entries each): one launch (k_dense_top)
         DenseTopCounts counts{};
         uint32_t n_top = 0;
-        while (n_top < 8 && level_from - n_top >= 1 && plan.n_level[level_from - n_top - 1] <= top_max) {
+        while (n_top < 8 && level_from - n_top >= 1 && plan.n_level[level_from - n_top - 1] <= kDenseTopMax) {
             counts.n[n_top] = uint32_t(plan.n_level[level_from - n_top - 1]);
             ++n_top;
         }
@@ -1097,7 +1064,6 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     }
     for (uint32_t level = level_from; level >= 1; --level) {
         const uint32_t nn = uint32_t(plan.n_level[level - 1]);
-        if (div_up(nn, 256) > narrow_max_wg) IPCFP_HIP(ctx, widen());
         hipLaunchKernelGGL(k_dense_level, dim3(div_up(nn, 256)), dim3(256), 0, ctx->stream, view, src, plan.roots, level, nn, a, anomaly_d,
                            set_err);
         set_err = nullptr;
@@ -1121,7 +1087,6 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
     // streams (host/verify_fast.cpp: the message keys feed the execution-order kernels on the main stream, the receipt
     // leaves feed k_receipt_events on the aux stream) forks here: k_dense_leaves goes to `leaves_stream`, ordered behind
     // the last interior level by `fork_event`, and runs beside k_dense_link_leaves instead of after it.
-    IPCFP_HIP(ctx, widen());
     if (set_err) IPCFP_HIP(ctx, hipMemsetAsync(set_err, 0xff, sizeof *set_err, ctx->stream));  // (no interior level: the roots are leaves)
     hipStream_t ls = ctx->stream;
     if (leaves_stream && leaves_stream != ctx->stream && fork_event) {

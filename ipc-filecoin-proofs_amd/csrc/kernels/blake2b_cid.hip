@@ -41,7 +41,6 @@ namespace ipcfp {
 __device__ __forceinline__ uint32_t chunk_count(uint32_t len) { return len == 0 ? 1u : (len + 127u) >> 7; }
 
 // Shared body: hash block `i`, leaving the state in h[].
-template <int MODE>
 __device__ __forceinline__ void hash_block(const uint8_t* __restrict__ arena, uint64_t o, uint32_t L,
                                            uint64_t h[8]) {
     b2b::init256(h);
@@ -54,46 +53,18 @@ __device__ __forceinline__ void hash_block(const uint8_t* __restrict__ arena, ui
         uint64_t mn[16];
         b2b::load_chunk(mn, p + 128ull * (c + 1));  // c+1 <= nfull: inside the block's padded span
         t += 128;
-        b2b::compress<MODE>(h, m, t, false);
+        b2b::compress(h, m, t, false);
 #pragma unroll
         for (int k = 0; k < 16; ++k) m[k] = mn[k];
     }
     const uint32_t rem = L - nfull * 128u;  // 0 (empty message) .. 128
     b2b::mask_tail(m, rem);
     t += rem;
-    b2b::compress<MODE>(h, m, t, true);
-}
-
-// The LDS-message variant of hash_block: the chunk being compressed lives in LDS ([word][lane]), the next one is
-// prefetched into registers while it is compressed.
-template <int WG>
-__device__ __forceinline__ void hash_block_lds(const uint8_t* __restrict__ arena, uint64_t o, uint32_t L, uint64_t h[8],
-                                               uint64_t (*sm)[WG]) {
-    b2b::init256(h);
-    const uint8_t* p = arena + o;
-    const uint32_t nfull = chunk_count(L) - 1;  // non-final chunks
-    uint64_t* lm = &sm[0][threadIdx.x];
-    uint64_t m[16];
-    b2b::load_chunk(m, p);
-    uint64_t t = 0;
-    for (uint32_t c = 0; c < nfull; ++c) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lm[k * WG] = m[k];
-        b2b::load_chunk(m, p + 128ull * (c + 1));  // in flight while the staged chunk is compressed
-        t += 128;
-        b2b::compress_lds(h, lm, WG, t, false);
-    }
-    const uint32_t rem = L - nfull * 128u;
-    b2b::mask_tail(m, rem);
-    t += rem;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) lm[k * WG] = m[k];
-    b2b::compress_lds(h, lm, WG, t, true);
+    b2b::compress(h, m, t, true);
 }
 
 // K1's per-lane metadata (K1Meta, witness_dev.h) is stored in SCHEDULE order so a wavefront reads it coalesced.
 
-template <int MODE>
 __global__ __launch_bounds__(256, IPCFP_K1_WAVES) void k_blake2b256_cid(const uint8_t* __restrict__ arena,
                                                        const K1Meta* __restrict__ meta,
                                                        const uint8_t* __restrict__ sched_cids40, uint32_t n,
@@ -113,37 +84,7 @@ __global__ __launch_bounds__(256, IPCFP_K1_WAVES) void k_blake2b256_cid(const ui
     uint8_t st = IPCFP_CID_UNCHECKED;
     if (is_b2b) {
         uint64_t h[8];
-        hash_block<MODE>(arena, mt.off, mt.len, h);
-        const uint64_t e0 = (w0 >> 48) | (w1 << 16);
-        const uint64_t e1 = (w1 >> 48) | (w2 << 16);
-        const uint64_t e2 = (w2 >> 48) | (w3 << 16);
-        const uint64_t e3 = (w3 >> 48) | (w4 << 16);
-        const bool ok = ((h[0] ^ e0) | (h[1] ^ e1) | (h[2] ^ e2) | (h[3] ^ e3)) == 0;
-        st = ok ? IPCFP_CID_OK : IPCFP_CID_MISMATCH;
-        if (ok) atomicOr(&ok_bits[i >> 5], 1u << (i & 31));
-        else atomicAdd(&counters[0], 1ull);
-    }
-    status[i] = st;
-}
-
-// K1 with the message words staged in LDS (IPCFP_B2B_MODE=3): same outputs, 64 threads per workgroup.
-__global__ __launch_bounds__(64, 5) void k_blake2b256_cid_lds(const uint8_t* __restrict__ arena, const K1Meta* __restrict__ meta,
-                                                              const uint8_t* __restrict__ sched_cids40, uint32_t n,
-                                                              uint32_t* __restrict__ ok_bits, uint8_t* __restrict__ status,
-                                                              unsigned long long* __restrict__ counters) {
-    __shared__ uint64_t sm[16][64];
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const K1Meta mt = meta[t];
-    const uint32_t i = mt.id;
-    const uint64_t* cw = reinterpret_cast<const uint64_t*>(sched_cids40 + 40ull * t);
-    const uint64_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3], w4 = cw[4];
-    const bool is_b2b = ((w0 & 0x0000FFFFFFFF00FFULL) == 0x00002002e4a00001ULL) && ((w0 & 0x8000ULL) == 0) &&
-                        ((w4 >> 48) == 0);
-    uint8_t st = IPCFP_CID_UNCHECKED;
-    if (is_b2b) {
-        uint64_t h[8];
-        hash_block_lds<64>(arena, mt.off, mt.len, h, sm);
+        hash_block(arena, mt.off, mt.len, h);
         const uint64_t e0 = (w0 >> 48) | (w1 << 16);
         const uint64_t e1 = (w1 >> 48) | (w2 << 16);
         const uint64_t e2 = (w2 >> 48) | (w3 << 16);
@@ -157,7 +98,6 @@ __global__ __launch_bounds__(64, 5) void k_blake2b256_cid_lds(const uint8_t* __r
 }
 
 // Raw digests (ipcfp_blake2b256_batch): out32[id] = Blake2b-256(block).
-template <int MODE>
 __global__ __launch_bounds__(256) void k_blake2b256_raw(const uint8_t* __restrict__ arena,
                                                        const K1Meta* __restrict__ meta, uint32_t n,
                                                        uint64_t* __restrict__ out32) {
@@ -165,7 +105,7 @@ __global__ __launch_bounds__(256) void k_blake2b256_raw(const uint8_t* __restric
     if (t >= n) return;
     const K1Meta mt = meta[t];
     uint64_t h[8];
-    hash_block<MODE>(arena, mt.off, mt.len, h);
+    hash_block(arena, mt.off, mt.len, h);
     uint64_t* o = out32 + 4ull * mt.id;
     o[0] = h[0];
     o[1] = h[1];
@@ -289,6 +229,8 @@ __global__ __launch_bounds__(256) void k_chunk_scatter(const uint32_t* __restric
 }
 
 // ------------------------------ launchers -----------------------------------
+constexpr uint32_t kK1Wg = 64;  // threads per workgroup of the two hash kernels (64-256 measured: profiles/r01_k1_tune_first.log)
+
 int launch_chunk_order(ipcfp_ctx* ctx, const uint32_t* len_d, uint32_t n, uint32_t* bins_d /*256*/,
                        uint32_t* order_d) {
     IPCFP_HIP(ctx, hipMemsetAsync(bins_d, 0, 256 * sizeof(uint32_t), ctx->stream));
@@ -339,20 +281,8 @@ int launch_blake2b256_cid(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta
     if (n == 0) return IPCFP_OK;
     {
         ProfileScope prof(ctx, IPCFP_K_BLAKE2B_CID, s);
-        const uint32_t wg = ctx->b2b_wg;
-        const K1Meta* m = static_cast<const K1Meta*>(meta);
-        if (ctx->b2b_mode == 1)
-            hipLaunchKernelGGL(k_blake2b256_cid<1>, dim3(div_up(n, wg)), dim3(wg), 0, s, arena, m, sched_cids40, n, ok_bits,
-                               status, counters);
-        else if (ctx->b2b_mode == 2)
-            hipLaunchKernelGGL(k_blake2b256_cid<2>, dim3(div_up(n, wg)), dim3(wg), 0, s, arena, m, sched_cids40, n, ok_bits,
-                               status, counters);
-        else if (ctx->b2b_mode == 3)
-            hipLaunchKernelGGL(k_blake2b256_cid_lds, dim3(div_up(n, 64)), dim3(64), 0, s, arena, m, sched_cids40, n, ok_bits,
-                               status, counters);
-        else
-            hipLaunchKernelGGL(k_blake2b256_cid<0>, dim3(div_up(n, wg)), dim3(wg), 0, s, arena, m, sched_cids40, n, ok_bits,
-                               status, counters);
+        hipLaunchKernelGGL(k_blake2b256_cid, dim3(div_up(n, kK1Wg)), dim3(kK1Wg), 0, s, arena, static_cast<const K1Meta*>(meta),
+                           sched_cids40, n, ok_bits, status, counters);
     }
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
@@ -362,14 +292,8 @@ int launch_blake2b256_raw(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta
     if (n == 0) return IPCFP_OK;
     {
         ProfileScope prof(ctx, IPCFP_K_BLAKE2B_RAW);
-        const uint32_t wg = ctx->b2b_wg;
-        const K1Meta* m = static_cast<const K1Meta*>(meta);
-        if (ctx->b2b_mode == 1)
-            hipLaunchKernelGGL(k_blake2b256_raw<1>, dim3(div_up(n, wg)), dim3(wg), 0, ctx->stream, arena, m, n,
-                               reinterpret_cast<uint64_t*>(out32));
-        else
-            hipLaunchKernelGGL(k_blake2b256_raw<0>, dim3(div_up(n, wg)), dim3(wg), 0, ctx->stream, arena, m, n,
-                               reinterpret_cast<uint64_t*>(out32));
+        hipLaunchKernelGGL(k_blake2b256_raw, dim3(div_up(n, kK1Wg)), dim3(kK1Wg), 0, ctx->stream, arena,
+                           static_cast<const K1Meta*>(meta), n, reinterpret_cast<uint64_t*>(out32));
     }
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;

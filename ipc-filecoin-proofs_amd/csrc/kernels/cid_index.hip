@@ -9,36 +9,25 @@
 // linear probing; keys are compared against the cids[] array (5 × u64 per CID).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../common.h"
 #include "launch.h"
 #include "witness_dev.h"
 
 namespace ipcfp {
 
-// `done`: every workgroup counts itself when its keys are in (all its atomics have returned by then), so that a reader on
-// another stream can tell a key that is not in the table YET from one that never will be (tipset_prepare.hip LiveIndex).
-template <bool CAS_FIRST>
 __global__ __launch_bounds__(256) void k_index_insert(const uint8_t* __restrict__ cids, uint32_t n,
-                                                      uint32_t* __restrict__ slots, uint32_t mask, uint32_t* __restrict__ done) {
+                                                      uint32_t* __restrict__ slots, uint32_t mask) {
     // workgroups are handed out in blockIdx order: the even ones take the table of CIDs from the front, the odd ones from
     // the back, so that BOTH ends of the witness are in within the first microseconds — a recorded witness holds the
-    // headers and roots first (they are read first), one built bottom-up holds them last, and the tipset prologue on the
-    // head stream is waiting for exactly those keys
+    // headers and roots first (they are read first), one built bottom-up holds them last
     const uint32_t wg = (blockIdx.x & 1u) ? gridDim.x - 1u - (blockIdx.x >> 1) : (blockIdx.x >> 1);
     const uint32_t i = wg * blockDim.x + threadIdx.x;
-    if (i < n) index_insert_key<CAS_FIRST>(cids, slots, mask, i);
-    if (done) {  // (only a context with a head stream has a reader for the count)
-        __syncthreads();
-        if (threadIdx.x == 0) atomicAdd(done, 1u);
-    }
+    if (i < n) index_insert_key(cids, slots, mask, i);
 }
 
 int launch_index_insert(ipcfp_ctx* ctx, const uint8_t* cids_d, uint32_t n, uint32_t* slots_d, uint32_t mask) {
     if (n == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_index_insert<true>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, cids_d, n, slots_d, mask,
-                       static_cast<uint32_t*>(nullptr));
+    hipLaunchKernelGGL(k_index_insert, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, cids_d, n, slots_d, mask);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
@@ -54,29 +43,9 @@ int witness_build_index(ipcfp_ctx* ctx, ipcfp_witness* w) {
     if (w->index_slots.count != size) IPCFP_HIP(ctx, w->index_slots.alloc(size));  // rebuilds reuse the table
     w->index_mask = size - 1;
     IPCFP_HIP(ctx, hipMemsetAsync(w->index_slots.p, 0xff, size_t(size) * 4, ctx->stream));
-    w->index_wgs = div_up(n, 256);
-    if (ctx->stream_head) {  // the insert workgroups count themselves done; "the table is cleared": where a lookup on the head stream may start
-        if (!w->index_done.p) IPCFP_HIP(ctx, w->index_done.alloc_unpooled(1));
-        IPCFP_HIP(ctx, hipMemsetAsync(w->index_done.p, 0, 4, ctx->stream));
-        if (!w->index_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&w->index_event, hipEventDisableTiming));
-        IPCFP_HIP(ctx, hipEventRecord(w->index_event, ctx->stream));
-    }
     if (n == 0) return IPCFP_OK;
-    {
-        ProfileScope prof(ctx, IPCFP_K_CID_INDEX);
-        static const bool cas_first = [] {
-            const char* e = std::getenv("IPCFP_INDEX_CAS_FIRST");
-            return !(e && std::atoi(e) == 0);
-        }();
-        if (cas_first)
-            hipLaunchKernelGGL(k_index_insert<true>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w->cids.p, n,
-                               w->index_slots.p, w->index_mask, w->index_done.p);
-        else
-            hipLaunchKernelGGL(k_index_insert<false>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w->cids.p, n,
-                               w->index_slots.p, w->index_mask, w->index_done.p);
-    }
-    IPCFP_HIP(ctx, hipGetLastError());
-    return IPCFP_OK;
+    ProfileScope prof(ctx, IPCFP_K_CID_INDEX);
+    return launch_index_insert(ctx, w->cids.p, n, w->index_slots.p, w->index_mask);
 }
 
 }  // namespace ipcfp

@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "../common.h"
 #include "launch.h"
@@ -914,11 +913,9 @@ int launch_hamt_get_levels(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& r
     // node's children itself (level after level, the small-stage instance alone: a link node is 1.4 KB) and ONE advance
     // launch takes every query down all of them.  How many levels: all but the last three the call queues (the bucket level
     // and two of overflow nodes), at most three, and only while a level's worst case fits a list.
-    static const int top_env = [] { const char* e = std::getenv("IPCFP_HAMT_TOP"); return e ? std::atoi(e) : -1; }();
     uint32_t top = 0;
-    if (actor && levels >= 4 && bit_width == 5 && top_env != 0) {
+    if (actor && levels >= 4 && bit_width == 5) {
         top = std::min(levels - 3u, 3u);
-        if (top_env > 0) top = std::min(uint32_t(top_env), levels - 1u);
         while (top > 0 && (1ull << (bit_width * (top - 1u))) > cap) --top;
     }
     auto parse_grid = [&](uint32_t lv, uint32_t per_cu, uint32_t nodes_per_wg = kCoopNodes) {
@@ -943,10 +940,8 @@ int launch_hamt_get_levels(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& r
         hipLaunchKernelGGL(k_hamt_lv_advance_top, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w, L, top, bit_width, vkind, keys_d, key_off_d,
                            key_len_d, n, status_d, loc);
     // Below the fused top the SHORT nodes (the overflow nodes under full buckets) keep the 32-lane form, two nodes per
-    // wavefront.  IPCFP_HAMT_SMALL_LANE=1 (A/B): one lane each with the line-staged reader (hamt_table_lane.hip) — measured
-    // and off: 182 µs for the overflow level against ≈ 100, and its nodes have no entry table, so the advance behind it
-    // walks the bucket with the reader (42 µs against 12): profiles/r06_experiments.md.
-    static const bool small_lane = [] { const char* e = std::getenv("IPCFP_HAMT_SMALL_LANE"); return e && std::atoi(e) == 1; }();
+    // wavefront.  (One lane each with the line-staged reader was measured and is slower: 182 µs for the overflow level
+    // against ≈ 100, and the advance behind it has no entry table to read — profiles/r06_experiments.md.)
     for (uint32_t lv = top; lv < levels; ++lv) {
         if (actor) {
             // Which class a level's nodes fall into is the tree's business, but the odds are known: the first level below
@@ -955,18 +950,11 @@ int launch_hamt_get_levels(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& r
             // an empty list then costs ≈ 4 µs instead of ≈ 9 (32 k workgroups that read one word each).
             const bool bucket_level = top > 0 && lv == top;
             const uint32_t narrow = 1024u;
-            static const bool small8 = [] { const char* e = std::getenv("IPCFP_HAMT_SMALL8"); return !(e && std::atoi(e) == 0); }();
-            const bool eight = small8 && top > 0;  // (eight lanes per short node below a fused top: hamt_parse_actor_pair LANES)
+            const bool eight = top > 0;  // (eight lanes per short node below a fused top: hamt_parse_actor_pair LANES)
             const uint32_t g_small = top > 0 && bucket_level ? std::min(parse_grid(lv, 32, eight ? 8u : kCoopNodes), narrow)
                                                              : parse_grid(lv, 32, eight ? 8u : kCoopNodes);
             const uint32_t g_long = top > 0 && !bucket_level ? std::min(parse_grid(lv, 14), narrow) : parse_grid(lv, 14);
-            if (small_lane && top > 0) {
-                uint64_t fan = 1;
-                for (uint32_t k = 0; k < lv && fan < cap; ++k) fan <<= bit_width;
-                const int rc = launch_hamt_lv_parse_lane(ctx, w, L.work[lv & 1u][0], L.count + kHamtClasses * lv, cap, fan < cap ? uint32_t(fan) : cap,
-                                                         HK_ACTOR_STATE, recs_d, L.etab_of);
-                if (rc) return rc;
-            } else if (eight) {
+            if (eight) {
                 hipLaunchKernelGGL((k_hamt_lv_parse_actor<kCoopSmallStage, kCoopSmallEntries, 0u, false, 8u>), dim3(g_small), dim3(64), 0,
                                    ctx->stream, w, L, lv);
             } else {

@@ -12,8 +12,6 @@
 #define IPCFP_RD_RING 8
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../common.h"
 #include "cbor_dev.h"
 #include "hamt_table_body.h"

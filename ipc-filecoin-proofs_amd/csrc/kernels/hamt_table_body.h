@@ -82,7 +82,7 @@ __device__ __forceinline__ void hamt_node_parse(Rd& r, uint32_t kinds, bool writ
                     // elements — from two fetches and one more per four elements.  Item by item it is four heads and an element
                     // loop, ≈ 2.7 k instructions, and one lane does that for the ≈ 8 entries of its node: 0.6 ms of configs[4]'s
                     // call for k_hamt_node_table_lane (profiles/r06_experiments.md).  Anything else takes that way as before.
-                    if ((kinds & (HK_VEC_U8 | HK_ITEM_BY_ITEM)) == HK_VEC_U8) {
+                    if (kinds & HK_VEC_U8) {
                         const uint32_t e0 = r.pos;
                         if (e0 + 36u <= r.n && (r.peek64(e0) & 0xffffffull) == 0x205882ull) {
                             const uint32_t end = vec_u8_end(r, e0 + 35u);

@@ -48,9 +48,6 @@ int launch_hamt_get(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& root, ui
                     uint8_t* status_d, void* loc_d, int pending_only = 0);
 // --- hamt_levels.hip --- K7 level by level: every visited node decoded once; what it leaves kStPending is the walker's
 size_t hamt_levels_scratch_words(uint32_t n, uint32_t n_blocks, uint32_t levels);
-// one lane per SHORT node of a level's work list (hamt_table_lane.hip; list entries {block, length, offset lo, offset hi})
-int launch_hamt_lv_parse_lane(ipcfp_ctx* ctx, const WitnessView& w, const void* list_d, const uint32_t* count_d, uint32_t cap, uint32_t bound,
-                              uint32_t kind_bit, void* recs_d, uint32_t* etab_of_d);
 int launch_hamt_get_levels(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& root, uint32_t bit_width, int vkind,
                            const uint8_t* keys_d, const uint32_t* key_off_d, const uint32_t* key_len_d, uint32_t n,
                            uint8_t* status_d, void* loc_d, uint32_t levels, uint32_t* scratch_d, void* recs_d, bool coop = true,
@@ -97,7 +94,7 @@ int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const 
 int launch_storage_run_actors_lane(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, void* runs_d, uint32_t n_runs,
                                    uint32_t undecided);
 int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, uint32_t n,
-                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut,
+                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d,
                                 const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d);
 int launch_verify_storage_lanes(ipcfp_ctx* ctx, const WitnessView& w, const ColumnClaimSrc& cols, const uint32_t* run_of_d, uint32_t n,
                                 const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only);
@@ -125,7 +122,7 @@ struct EventRec;
 struct EventTableView;
 struct LeafRef;
 struct EventClaimPacked;
-int launch_ctx_headers(ipcfp_ctx* ctx, const WitnessView& w, TipsetCtxDev* ctxs_d, uint32_t n);
+int launch_ctx_headers(ipcfp_ctx* ctx, const WitnessView& w, TipsetCtxDev* ctxs_d, uint32_t n);  // tipset_prepare_general.hip
 struct CtxFinish;
 int launch_ctx_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a);
 // the flags' prefix sum (decoupled look-back), positions (pos_d), inverse, total (total_d) and the context's tail in one
@@ -138,11 +135,10 @@ int launch_exec_insert_flags(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, u
                              uint32_t* first_d);
 int launch_exec_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const uint64_t* total_d, const uint32_t* first_d,
                        const uint32_t* pos_d, uint32_t n, uint32_t* inv_d);
+// the tipset prologue (tipset_prepare.hip; launchers and the general companion in tipset_prepare_general.hip)
 // jobs_d: device array of {TipsetCtxDev* ctx, AmtRootSpec* roots (nullable), unsigned long long* err}
-// live_done / live_total / anomaly: the CID index is still being filled on another stream (tipset_prepare.hip LiveIndex)
 int launch_tipset_prepare(ipcfp_ctx* ctx, const WitnessView& w, const void* jobs, const void* jobs_d, uint32_t n_jobs,
-                          bool need_general, const uint32_t* live_done = nullptr, uint32_t live_total = 0,
-                          uint32_t* anomaly = nullptr, bool defer_rehash = false,  // defer_rehash: see tipset_ctx.h txmeta_block
+                          bool need_general, bool defer_rehash = false,  // defer_rehash: see tipset_ctx.h txmeta_block
                           const void* inline_inputs = nullptr);  // host TipsetInputs of the one context: sent as a kernel argument
 int launch_exec_roots(ipcfp_ctx* ctx, const WitnessView& w, const TipsetCtxDev* ctx_d, AmtRootSpec* roots_d,
                       unsigned long long* err_d, int verify_txmeta = 1, uint32_t n_parents = 0);

@@ -61,7 +61,8 @@ static_assert(IPCFP_SRUN_FLAG_MASK == (SC_CHILD_PARSED | SC_STATE_ROOT_CANON | S
               "flag split");
 
 // The per-run word the claim kernel reads beside its run's record (run_match): bits 0-2 the three claimed-vs-derived
-// CID comparisons, 8 = nobody has compared (plain route without k_storage_run_children).  The column route adds what a
+// CID comparisons, made once per run by k_storage_run_children (8 = nobody has compared: no launcher leaves a run at
+// that any more; k_verify_storage_table still reads it, its body being kept as it was).  The column route adds what a
 // claim would otherwise fetch from the run table: its CID flag bits, the trust policy's answer for the run's epoch,
 // and whether the record carries bits nobody knows.
 enum : uint32_t {

@@ -11,7 +11,7 @@
 // instructions of the windowed reader the same parse needs on global memory.
 //
 // A block that does not fit the stage is not parsed here: the slot is flagged in TipsetCtxDev::prologue_general and
-// k_tipset_prepare_general (verify_events.hip), launched right behind, does that slot the general way.
+// k_tipset_prepare_general (tipset_prepare_general.hip), launched right behind, does that slot the general way.
 #define IPCFP_RD_LDS 1
 #include <hip/hip_runtime.h>
 
@@ -20,82 +20,12 @@
 #include "claims_dev.h"
 #include "header_dev.h"
 #include "tipset_ctx.h"
+#include "txmeta_dev.h"
 
 namespace ipcfp {
 
 
 typedef __attribute__((address_space(3))) const uint8_t* lds_bytes_t;
-
-// ---- lookups in an index that is still being filled ---------------------------------------------------------------------
-// k_index_insert (main stream) fills the table while the prologue's wavefronts (head stream, host/verify_fast.cpp) look
-// their few CIDs up: the prologue is a chain of dependent steps per slot — look the header up, stage it, decode ≈ 100
-// CBOR items on one lane, look the TxMeta up, decode it, re-hash it — ≈ 130 µs that used to start when the ≈ 120 µs of
-// inserts had finished.  Such a lookup
-// can only err one way: a key that is not in the table YET (an entry never moves and the slots in front of it never
-// empty, so a key that is in is found), or — a CID that occurs twice — an id that a later insert still raises.  So a
-// miss is retried until the key shows up or every insert workgroup has counted itself done, whatever was found is
-// taken as provisional, and at the end of its slot the wavefront waits for the count and looks every key up once more:
-// a different answer (or a wait that ran out) raises the call's anomaly flag, and the caller does the batch again the
-// general way.  Reads of the table are device-scope atomic loads (other XCDs' L2s are filling it).
-constexpr uint32_t kLiveSpinMax = 1u << 21;  // ≈ 2 s of 1 µs naps: a launch that cannot finish must not hang the device
-struct LiveIndex {
-    const uint32_t* done;  // workgroups of the insert part that have finished; null: the index is complete (plain lookups)
-    uint32_t total;
-    uint32_t n_used;
-    bool failed;
-    CidKey k0, k1;  // (two named slots, not an array: a dynamically indexed member would live in scratch)
-    uint32_t b0, b1;
-};
-__device__ __forceinline__ uint32_t live_probe(const WitnessView& w, const CidKey& key) {
-    uint32_t s = cid_hash(key) & w.mask;
-    for (;;) {
-        const uint32_t b = __hip_atomic_load(&w.slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (b == kNoBlock) return kNoBlock;
-        if (cid_equal(load_cid_slot(w.cids, b), key)) return b;
-        s = (s + 1) & w.mask;
-    }
-}
-__device__ __forceinline__ bool live_complete(const LiveIndex& li) {
-    return __hip_atomic_load(li.done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= li.total;
-}
-// every lane of the wavefront, same key
-__device__ __forceinline__ uint32_t find_block(const WitnessView& w, LiveIndex& li, const CidKey& key) {
-    if (!li.done) return witness_find(w, key);
-    uint32_t b = kNoBlock;
-    for (uint32_t spin = 0;; ++spin) {
-        const bool complete = live_complete(li);  // read BEFORE the probe: a miss after `complete` is final
-        b = live_probe(w, key);
-        if (b != kNoBlock || complete) break;
-        if (spin >= kLiveSpinMax) {
-            li.failed = true;
-            break;
-        }
-        __builtin_amdgcn_s_sleep(32);
-    }
-    if (li.n_used == 0) {
-        li.k0 = key;
-        li.b0 = b;
-    } else if (li.n_used == 1) {
-        li.k1 = key;
-        li.b1 = b;
-    } else {
-        li.failed = true;
-    }
-    ++li.n_used;
-    return b;
-}
-// end of a slot: the provisional answers against the finished index
-__device__ __forceinline__ void live_validate(const WitnessView& w, LiveIndex& li, uint32_t* anomaly) {
-    if (!li.done) return;
-    bool bad = li.failed;
-    for (uint32_t spin = 0; !bad && !live_complete(li); ++spin) {
-        if (spin >= kLiveSpinMax) bad = true;
-        __builtin_amdgcn_s_sleep(32);
-    }
-    if (!bad && li.n_used > 0) bad = live_probe(w, li.k0) != li.b0;
-    if (!bad && li.n_used > 1) bad = live_probe(w, li.k1) != li.b1;
-    if (bad && threadIdx.x == 0) atomicOr(anomaly, 1u);
-}
 
 // every lane of the wavefront: block b → the stage; false when it does not fit
 __device__ __forceinline__ bool stage_block(const WitnessView& w, uint32_t b, rd_chunk_t* stage, uint32_t& len) {
@@ -112,17 +42,17 @@ __device__ __forceinline__ void flag_general(TipsetCtxDev& c, uint32_t slot) {
     if (threadIdx.x == 0) atomicOr(&c.prologue_general, 1ull << slot);
 }
 
-// slots 0 / 1: the child header / the first parent header (ctx_headers_body in verify_events.hip is the general form)
+// slots 0 / 1: the child header / the first parent header (ctx_headers_body in tipset_prepare_general.hip is the general form)
 // (`in`: the context's inputs — its own head in device memory, or the kernel argument)
 __device__ __forceinline__ void headers_slot(const WitnessView& w, const TipsetInputs& in, TipsetCtxDev& c, bool child_part,
-                                             rd_chunk_t* stage, AmtRootSpec* receipts_spec, LiveIndex& li) {
+                                             rd_chunk_t* stage, AmtRootSpec* receipts_spec) {
     const bool lead = threadIdx.x == 0;
     const bool parsed = (in.flags & (TC_PARENTS_PARSED | TC_CHILD_PARSED)) == (TC_PARENTS_PARSED | TC_CHILD_PARSED);
     uint32_t status = IPCFP_ST_ERR_BAD_CLAIM, match = 0;
     long long height = 0;
     const bool wanted = parsed && (child_part || in.n_parents > 0);
     if (wanted) {
-        const uint32_t hb = find_block(w, li, child_part ? in.child : in.parents[0]);  // uniform across the wavefront
+        const uint32_t hb = witness_find(w, child_part ? in.child : in.parents[0]);  // uniform across the wavefront
         if (hb == kNoBlock) {
             status = IPCFP_ST_ERR_MISSING_BLOCK;
         } else {
@@ -175,10 +105,10 @@ __device__ __forceinline__ void headers_slot(const WitnessView& w, const TipsetI
 }
 
 // slot 2 + b: parent block b → its header, its TxMeta (re-hashed), its two message-AMT roots
-// (exec_roots_body in verify_events.hip is the general form; error sequence numbers as there)
+// (exec_roots_body in tipset_prepare_general.hip is the general form; error sequence numbers as there)
 __device__ __forceinline__ void roots_slot(const WitnessView& w, const TipsetInputs& in, TipsetCtxDev& c,
                                            AmtRootSpec* __restrict__ roots, unsigned long long* __restrict__ err, uint32_t b,
-                                           rd_chunk_t* stage, LiveIndex& li, bool defer_rehash) {
+                                           rd_chunk_t* stage, bool defer_rehash) {
     __shared__ CidKey s_tx;
     __shared__ uint32_t s_have_tx;
     const uint32_t P = in.n_parents;
@@ -187,7 +117,7 @@ __device__ __forceinline__ void roots_slot(const WitnessView& w, const TipsetInp
     auto fail = [&](uint32_t seq, uint32_t code) { atomicMin(err, (unsigned long long)pack_enum_error(seq, 0, code)); };
     // reconstruct_execution_order (utils.rs:20-27): the parent header
     if (lead) s_have_tx = 0;
-    const uint32_t hb = find_block(w, li, in.parents[b]);
+    const uint32_t hb = witness_find(w, in.parents[b]);
     if (hb == kNoBlock) {
         if (lead) fail(b, IPCFP_ST_ERR_MISSING_BLOCK);
     } else {
@@ -216,7 +146,7 @@ __device__ __forceinline__ void roots_slot(const WitnessView& w, const TipsetInp
     bls.skip = secp.skip = 1;
     if (s_have_tx) {
         const CidKey tx = s_tx;
-        const uint32_t tb = find_block(w, li, tx);  // :58-60
+        const uint32_t tb = witness_find(w, tx);  // :58-60
         if (tb == kNoBlock) {
             if (lead) fail(seq, IPCFP_ST_ERR_MISSING_BLOCK);
         } else {
@@ -242,27 +172,8 @@ __device__ __forceinline__ void roots_slot(const WitnessView& w, const TipsetInp
                     bls.skip = secp.skip = 0;
                 } else {
                     // put_cbor(&(bls_root, secp_root), Blake2b256): canonical re-encoding, hashed (:65-72)
-                    uint8_t enc[200];
-                    uint32_t n = 0;
-                    enc[n++] = 0x82;
-                    const uint32_t offs[2] = {o0, o1}, lens[2] = {l0, l1};
-                    for (int k = 0; k < 2; ++k) {
-                        enc[n++] = 0xd8;
-                        enc[n++] = 0x2a;
-                        const uint32_t bl = lens[k] + 1;
-                        if (bl < 24) enc[n++] = uint8_t(0x40 | bl);
-                        else { enc[n++] = 0x58; enc[n++] = uint8_t(bl); }
-                        enc[n++] = 0x00;
-                        for (uint32_t i = 0; i < lens[k]; ++i) enc[n++] = uint8_t(r.at(offs[k] + i));
-                    }
-                    uint64_t d[4];
-                    blake2b256_small(enc, n, d);
                     CidKey re;
-                    re.w[0] = 0x00002002e4a07101ULL | (d[0] << 48);
-                    re.w[1] = (d[0] >> 16) | (d[1] << 48);
-                    re.w[2] = (d[1] >> 16) | (d[2] << 48);
-                    re.w[3] = (d[2] >> 16) | (d[3] << 48);
-                    re.w[4] = d[3] >> 16;
+                    txmeta_rehash(r, o0, l0, o1, l1, re);
                     if (!cid_equal(re, tx)) {  // (the verify path always checks: reconstruct_execution_order)
                         fail(seq, IPCFP_ST_ERR_TXMETA_MISMATCH);
                     } else {
@@ -280,12 +191,13 @@ __device__ __forceinline__ void roots_slot(const WitnessView& w, const TipsetInp
     }
 }
 
-// `live_done` non-null: the CID index is being filled beside this launch (LiveIndex above); `anomaly`: the call's flag.
 // INLINE: the one context's inputs are the kernel ARGUMENT `in0` (scalar loads from the kernarg segment); its device copy
 // — zeroed memory, not yet written by anyone — gets them from slot 0, for the kernels behind this launch.
+// (5 waves per SIMD, i.e. at most 96 VGPRs: what the INLINE instance — the verify step's — was allocated before the
+// live-index code left; without the bound the allocator gives the shorter kernel 101 / 103)
 template <bool INLINE>
-__global__ __launch_bounds__(64) void k_tipset_prepare(WitnessView w, PrepareJobs jobs, uint32_t n_jobs, const uint32_t* live_done,
-                                                       uint32_t live_total, uint32_t* anomaly, int defer_rehash, TipsetInputs in0) {
+__global__ __launch_bounds__(64, 5) void k_tipset_prepare(WitnessView w, PrepareJobs jobs, uint32_t n_jobs, int defer_rehash,
+                                                       TipsetInputs in0) {
     __shared__ rd_chunk_t stage[kPrologueStageChunks];
     const uint32_t job = blockIdx.x / kPrepareSlots, slot = blockIdx.x % kPrepareSlots;
     if (job >= n_jobs) return;
@@ -297,23 +209,18 @@ __global__ __launch_bounds__(64) void k_tipset_prepare(WitnessView w, PrepareJob
         uint64_t* dst = reinterpret_cast<uint64_t*>(jb.ctx);
         for (uint32_t i = threadIdx.x; i < sizeof(TipsetInputs) / 8; i += 64u) dst[i] = src[i];
     }
-    LiveIndex li{};
-    li.done = live_done;
-    li.total = live_total;
-    if (slot < 2) headers_slot(w, in, *jb.ctx, slot == 0, stage, jb.roots ? jb.roots + 2u * in.n_parents : nullptr, li);
-    else if (jb.roots) roots_slot(w, in, *jb.ctx, jb.roots, jb.err, slot - 2, stage, li, defer_rehash != 0);
-    live_validate(w, li, anomaly);
+    if (slot < 2) headers_slot(w, in, *jb.ctx, slot == 0, stage, jb.roots ? jb.roots + 2u * in.n_parents : nullptr);
+    else if (jb.roots) roots_slot(w, in, *jb.ctx, jb.roots, jb.err, slot - 2, stage, defer_rehash != 0);
 }
 
-void launch_tipset_prepare_lds(hipStream_t stream, const WitnessView& w, const PrepareJobs& jobs, uint32_t n_jobs,
-                               const uint32_t* live_done, uint32_t live_total, uint32_t* anomaly, bool defer_rehash,
+void launch_tipset_prepare_lds(hipStream_t stream, const WitnessView& w, const PrepareJobs& jobs, uint32_t n_jobs, bool defer_rehash,
                                const TipsetInputs* inline_inputs) {
     if (inline_inputs && n_jobs == 1)
-        hipLaunchKernelGGL(k_tipset_prepare<true>, dim3(kPrepareSlots), dim3(64), 0, stream, w, jobs, n_jobs, live_done, live_total,
-                           anomaly, defer_rehash ? 1 : 0, *inline_inputs);
+        hipLaunchKernelGGL(k_tipset_prepare<true>, dim3(kPrepareSlots), dim3(64), 0, stream, w, jobs, n_jobs, defer_rehash ? 1 : 0,
+                           *inline_inputs);
     else
-        hipLaunchKernelGGL(k_tipset_prepare<false>, dim3(n_jobs * kPrepareSlots), dim3(64), 0, stream, w, jobs, n_jobs, live_done,
-                           live_total, anomaly, defer_rehash ? 1 : 0, TipsetInputs{});
+        hipLaunchKernelGGL(k_tipset_prepare<false>, dim3(n_jobs * kPrepareSlots), dim3(64), 0, stream, w, jobs, n_jobs,
+                           defer_rehash ? 1 : 0, TipsetInputs{});
 }
 
 }  // namespace ipcfp

@@ -13,6 +13,7 @@
 #include "amt_enum.h"
 #include "event_table.h"
 #include "tipset_ctx.h"
+#include "txmeta_dev.h"
 #include "types_dev.h"
 #include "launch.h"
 
@@ -166,27 +167,8 @@ __device__ __forceinline__ void exec_roots_body(const WitnessView& w, const Tips
                     fail(seq, IPCFP_ST_ERR_DECODE);
                 } else {
                     // put_cbor(&(bls_root, secp_root), Blake2b256): canonical re-encoding, hashed (:65-72)
-                    uint8_t enc[200];
-                    uint32_t n = 0;
-                    enc[n++] = 0x82;
-                    const uint32_t offs[2] = {o0, o1}, lens[2] = {l0, l1};
-                    for (int k = 0; k < 2; ++k) {
-                        enc[n++] = 0xd8;
-                        enc[n++] = 0x2a;
-                        const uint32_t bl = lens[k] + 1;
-                        if (bl < 24) enc[n++] = uint8_t(0x40 | bl);
-                        else { enc[n++] = 0x58; enc[n++] = uint8_t(bl); }
-                        enc[n++] = 0x00;
-                        for (uint32_t i = 0; i < lens[k]; ++i) enc[n++] = uint8_t(r.at(offs[k] + i));
-                    }
-                    uint64_t d[4];
-                    blake2b256_small(enc, n, d);
                     CidKey re;
-                    re.w[0] = 0x00002002e4a07101ULL | (d[0] << 48);
-                    re.w[1] = (d[0] >> 16) | (d[1] << 48);
-                    re.w[2] = (d[1] >> 16) | (d[2] << 48);
-                    re.w[3] = (d[2] >> 16) | (d[3] << 48);
-                    re.w[4] = d[3] >> 16;
+                    txmeta_rehash(r, o0, l0, o1, l1, re);
                     // verify_txmeta = false on the generation path (build_execution_order, utils.rs:44)
                     if (verify_txmeta && !cid_equal(re, tx[0])) {
                         fail(seq, IPCFP_ST_ERR_TXMETA_MISMATCH);
@@ -238,25 +220,21 @@ int launch_tipset_prepare_wide(ipcfp_ctx* ctx, const WitnessView& w, const void*
     return IPCFP_OK;
 }
 
-void launch_tipset_prepare_lds(hipStream_t stream, const WitnessView& w, const PrepareJobs& jobs, uint32_t n_jobs,
-                               const uint32_t* live_done, uint32_t live_total, uint32_t* anomaly, bool defer_rehash,
+void launch_tipset_prepare_lds(hipStream_t stream, const WitnessView& w, const PrepareJobs& jobs, uint32_t n_jobs, bool defer_rehash,
                                const TipsetInputs* inline_inputs);  // tipset_prepare.hip
 
 // `jobs`: HOST array; `jobs_d`: device copy, needed (and read) only when there are more than kInlineJobs.
 // `need_general`: some block of the witness may exceed the LDS stage, so the general companion has to look.
 int launch_tipset_prepare(ipcfp_ctx* ctx, const WitnessView& w, const void* jobs, const void* jobs_d, uint32_t n_jobs,
-                          bool need_general, const uint32_t* live_done, uint32_t live_total, uint32_t* anomaly,
-                          bool defer_rehash, const void* inline_inputs) {
+                          bool need_general, bool defer_rehash, const void* inline_inputs) {
     if (defer_rehash && need_general) return set_error(ctx, IPCFP_E_INVALID, "deferred TxMeta re-hash: LDS slots only");
-    if (live_done && (need_general || !anomaly)) return set_error(ctx, IPCFP_E_INVALID, "live prologue: LDS slots only");
     if (n_jobs == 0) return IPCFP_OK;
     PrepareJobs pj{};
     if (n_jobs <= kInlineJobs) std::memcpy(pj.inline_jobs, jobs, size_t(n_jobs) * sizeof(PrepareJob));
     else pj.more = static_cast<const PrepareJob*>(jobs_d);
     // (`inline_inputs`: the ONE context's TipsetInputs on the host — they ride in the kernel arguments and the context's
     // zeroed device copy is filled in by the launch itself)
-    launch_tipset_prepare_lds(ctx->stream, w, pj, n_jobs, live_done, live_total, anomaly, defer_rehash,
-                              static_cast<const TipsetInputs*>(inline_inputs));
+    launch_tipset_prepare_lds(ctx->stream, w, pj, n_jobs, defer_rehash, static_cast<const TipsetInputs*>(inline_inputs));
     if (need_general)
         hipLaunchKernelGGL(k_tipset_prepare_general, dim3(n_jobs * kPrepareSlots), dim3(64), 0, ctx->stream, w, pj, n_jobs);
     IPCFP_HIP(ctx, hipGetLastError());

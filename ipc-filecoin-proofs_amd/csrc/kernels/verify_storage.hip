@@ -8,8 +8,6 @@
 // which line decided.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../common.h"
 #include "claims_dev.h"
 #include "launch.h"
@@ -72,7 +70,7 @@ __device__ __forceinline__ uint32_t verify_storage_one(const WitnessView& w, con
 
 // WAVES = wavefronts per SIMD the register allocator must leave room for.  verify_storage_one inlines six
 // layout attempts, each a Keccak + SHA-256 + HAMT walk: at 4 waves (128 VGPRs) it spills 384 bytes per
-// lane to scratch, at 3 waves (168 VGPRs) it does not.  IPCFP_STORAGE_WAVES selects (default: see launch).
+// lane to scratch, at 3 waves (168 VGPRs) it does not; 4 measured fastest and is the one instantiated (verify_lanes).
 template <int WAVES, class Src>
 __global__ __launch_bounds__(256, WAVES) void k_verify_storage(WitnessView w, Src src, const uint32_t* __restrict__ run_of,
                                                                uint32_t n, ipcfp_trust_policy_t trust,
@@ -552,23 +550,22 @@ int launch_storage_run_actors_table(ipcfp_ctx* ctx, const WitnessView& w, const 
                                     uint32_t n_runs, uint32_t undecided) {
     return run_actors_table(ctx, w, table_d, cols, runs_d, n_runs, undecided);
 }
-// root_children_d: n_runs × 34 words of scratch (block of every run's root, the runs' CID matches, then 32 children per run), or null: every claim resolves its own
-// shortcut = false (column route only): the per-run words are made all the same — its claims have nothing else to compare with —
-// and every claim takes its own first step
+// root_children_d: n_runs × 34 words of scratch (block of every run's root, the runs' CID matches, then 32 children per run)
 template <class Src>
 static int verify_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const Src& src, uint32_t n, const uint32_t* run_of_d,
-                        const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut, const ipcfp_trust_policy_t& trust,
+                        const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, const ipcfp_trust_policy_t& trust,
                         uint32_t undecided, uint8_t* status_d) {
+    if (!root_children_d) return set_error(ctx, IPCFP_E_INVALID, "the tabled route needs its per-run words");
     uint32_t* root_block = root_children_d;
-    uint32_t* run_match = root_children_d ? root_children_d + n_runs : nullptr;
-    uint32_t* root_child = root_children_d ? root_children_d + 2 * size_t(n_runs) : nullptr;
-    if (root_children_d && n_runs)
+    uint32_t* run_match = root_children_d + n_runs;
+    uint32_t* root_child = root_children_d + 2 * size_t(n_runs);
+    if (n_runs)
         hipLaunchKernelGGL(k_storage_run_children<Src>, dim3(div_up(uint64_t(n_runs) * 32u, 256)), dim3(256), 0, ctx->stream, w,
                            static_cast<const HamtNodeRec*>(table_d), static_cast<const StorageRun*>(runs_d), n_runs, src, trust, root_block,
                            run_match, root_child);
     hipLaunchKernelGGL(k_verify_storage_table<Src>, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, w,
                        static_cast<const HamtNodeRec*>(table_d), src, n, run_of_d, static_cast<const StorageRun*>(runs_d),
-                       shortcut ? root_block : nullptr, run_match, shortcut ? root_child : nullptr, trust, undecided, status_d);
+                       root_block, run_match, root_child, trust, undecided, status_d);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }
@@ -576,13 +573,12 @@ int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void
                                 const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d,
                                 const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d) {
     return verify_table(ctx, w, table_d, PlainClaimSrc{static_cast<const StorageClaimPacked*>(claims_d)}, n, run_of_d, runs_d, n_runs,
-                        root_children_d, true, trust, undecided, status_d);
+                        root_children_d, trust, undecided, status_d);
 }
 int launch_verify_storage_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const ColumnClaimSrc& cols, uint32_t n,
-                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, bool shortcut,
+                                const uint32_t* run_of_d, const void* runs_d, uint32_t n_runs, uint32_t* root_children_d,
                                 const ipcfp_trust_policy_t& trust, uint32_t undecided, uint8_t* status_d) {
-    if (!root_children_d) return set_error(ctx, IPCFP_E_INVALID, "the column route needs its per-run words");
-    return verify_table(ctx, w, table_d, cols, n, run_of_d, runs_d, n_runs, root_children_d, shortcut, trust, undecided, status_d);
+    return verify_table(ctx, w, table_d, cols, n, run_of_d, runs_d, n_runs, root_children_d, trust, undecided, status_d);
 }
 
 int launch_storage_run_flags(ipcfp_ctx* ctx, const void* claims_d, uint32_t n, uint32_t* flag_d) {
@@ -616,15 +612,8 @@ int launch_storage_run_facts(ipcfp_ctx* ctx, const WitnessView& w, const ColumnC
 template <class Src>
 static int verify_lanes(ipcfp_ctx* ctx, const WitnessView& w, const Src& src, const uint32_t* run_of_d, uint32_t n,
                         const ipcfp_trust_policy_t& trust, uint8_t* status_d, int pending_only) {
-    static const int waves = [] {
-        const char* e = std::getenv("IPCFP_STORAGE_WAVES");
-        const int v = e ? std::atoi(e) : 4;
-        return v >= 2 && v <= 4 ? v : 4;
-    }();
     const dim3 g(div_up(n, 256)), blk(256);
-    if (waves == 2) hipLaunchKernelGGL((k_verify_storage<2, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
-    else if (waves == 3) hipLaunchKernelGGL((k_verify_storage<3, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
-    else hipLaunchKernelGGL((k_verify_storage<4, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
+    hipLaunchKernelGGL((k_verify_storage<4, Src>), g, blk, 0, ctx->stream, w, src, run_of_d, n, trust, status_d, pending_only);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }

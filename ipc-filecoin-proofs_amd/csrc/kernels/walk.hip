@@ -6,8 +6,6 @@
 // src/proofs/storage/decode.rs:81,88,96).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../common.h"
 #include "launch.h"
 #include "walk_dev.h"
@@ -65,13 +63,8 @@ __global__ __launch_bounds__(256) void k_hamt_get_table(WitnessView w, const Ham
 // on the 66 k-query batch of config 4 (one wavefront per SIMD at 64 queries each): 64 → 1.153 ms, 32 → 1.118 ms,
 // 16 → 1.857 ms, 8 → 2.441 ms — a SIMD issues a lone wavefront's instruction every ≈ 14 cycles and four wavefronts' every
 // ≈ 6, so halving the lanes once fills the gaps and halving them again only multiplies the instructions.  A batch that
-// leaves the chip under two wavefronts per SIMD therefore runs 32 queries per wavefront (IPCFP_HAMT_LANES overrides).
+// leaves the chip under two wavefronts per SIMD therefore runs 32 queries per wavefront.
 uint32_t hamt_lanes(const ipcfp_ctx* ctx, uint32_t n) {
-    static const int forced = [] {
-        const char* e = std::getenv("IPCFP_HAMT_LANES");
-        return e ? std::atoi(e) : 0;
-    }();
-    if (forced == 8 || forced == 16 || forced == 32 || forced == 64) return uint32_t(forced);
     const uint32_t simds = uint32_t(ctx->props.multiProcessorCount > 0 ? ctx->props.multiProcessorCount : 256) * 4u;
     return uint64_t(n) < uint64_t(simds) * 128u ? 32u : 64u;
 }
