@@ -149,7 +149,10 @@ int ipcfp_ctx_sync(ipcfp_ctx_t* ctx);
  *                  k > 0 exactly k levels whatever the batch size
  *   "hamt_coop"    0: the level path decodes ActorState nodes with one lane each instead of sixteen
  *   "hamt_table"   1: tabulate every block of the witness as a HAMT node first
- *   "fast_verify"  0: verify_event_proof never takes the route without mid-call synchronisation                     */
+ *   "fast_verify"  0: verify_event_proof never takes the route without mid-call synchronisation
+ *   "k1_resident", "parse_resident"   the grids of the CID check and of the block-order event parse: that many
+ *                  workgroups of 256 threads per CU, each looping over tiles of 256 blocks; 0: one workgroup per tile.
+ *                  0..16 (no -1: these two have a number as their default); anything else is IPCFP_E_INVALID        */
 int ipcfp_ctx_set_tuning(ipcfp_ctx_t* ctx, const char* key, int64_t value);
 /* Device properties used by the benchmarks: name (≤ 63 chars), CU count, HBM bytes. */
 int ipcfp_ctx_device_info(ipcfp_ctx_t* ctx, char name[64], int* cu_count, uint64_t* hbm_bytes);

@@ -420,7 +420,8 @@ class Engine:
             raise EngineError(f"{what}: {self.lib.ipcfp_strerror(rc).decode()} ({rc}) {msg}")
 
     def set_tuning(self, key: str, value: int):
-        """Route selection (ipcfp_ctx_set_tuning): "hamt_levels", "hamt_table", "fast_verify"."""
+        """Route selection (ipcfp_ctx_set_tuning): "hamt_levels", "hamt_table", "fast_verify"; the side grids'
+        workgroups per CU, "k1_resident" and "parse_resident" (0..16)."""
         self._check(self.lib.ipcfp_ctx_set_tuning(self.h, key.encode(), int(value)), "ctx_set_tuning")
 
     def sync(self):

@@ -39,7 +39,22 @@ struct ProfiledLaunch {
     hipEvent_t start, stop;
 };
 
+// Tiles of 256 schedule entries, as a grid: `resident` workgroups per CU that loop over the tiles, or (0) one per tile.
+constexpr uint32_t kResidentMax = 16;
+inline uint32_t resident_grid(uint32_t n_tiles, int resident, int cus) {
+    const uint64_t cap = uint64_t(resident > 0 ? resident : 0) * uint64_t(cus > 0 ? cus : 256);
+    return cap && cap < n_tiles ? uint32_t(cap) : n_tiles;
+}
+
 }  // namespace ipcfp
+
+// the defaults of the tuning keys "k1_resident" / "parse_resident": the best pair of profiles/resident_grids_sweep.txt
+#ifndef IPCFP_K1_RESIDENT_DEFAULT
+#define IPCFP_K1_RESIDENT_DEFAULT 0
+#endif
+#ifndef IPCFP_PARSE_RESIDENT_DEFAULT
+#define IPCFP_PARSE_RESIDENT_DEFAULT 1
+#endif
 
 // The opaque context of the C ABI.
 struct ipcfp_ctx {
@@ -142,6 +157,10 @@ struct ipcfp_ctx {
     int hamt_coop = -1;    // 0: the level path parses every node with one lane (kernels/hamt_levels.hip k_hamt_lv_parse) also for ActorState trees
     int hamt_table = -1;   // 1: tabulate EVERY block first (hamt_table.h; A/B measurements)
     int fast_verify = -1;  // 0: verify_event_proof never takes the no-synchronisation route (host/verify_fast.cpp)
+    // resident grids of the two side kernels: workgroups of 256 threads per CU, each looping over the tiles of 256 schedule
+    // entries that fall to it; 0: one workgroup per tile (kernels/blake2b_cid.hip, kernels/block_events.hip)
+    int k1_resident = IPCFP_K1_RESIDENT_DEFAULT;
+    int parse_resident = IPCFP_PARSE_RESIDENT_DEFAULT;
     void* hamt_recs = nullptr;
     size_t hamt_recs_bytes = 0;
     void* hamt_scratch = nullptr;

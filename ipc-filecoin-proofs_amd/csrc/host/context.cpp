@@ -278,6 +278,12 @@ int ipcfp_ctx_set_tuning(ipcfp_ctx_t* ctx, const char* key, int64_t value) {
     else if (k == "hamt_table") ctx->hamt_table = int(value);
     else if (k == "hamt_coop") ctx->hamt_coop = int(value);
     else if (k == "fast_verify") ctx->fast_verify = int(value);
+    else if (k == "k1_resident" || k == "parse_resident") {
+        // workgroups of 256 threads per CU of k_blake2b256_cid / k_block_events; 0: one workgroup per tile
+        if (value < 0 || value > int64_t(kResidentMax))
+            return set_error(ctx, IPCFP_E_INVALID, "tuning key '%s': %lld is outside 0..%u", key, (long long)value, kResidentMax);
+        (k == "k1_resident" ? ctx->k1_resident : ctx->parse_resident) = int(value);
+    }
     else return set_error(ctx, IPCFP_E_INVALID, "unknown tuning key '%s'", key);
     return IPCFP_OK;
 }

@@ -28,7 +28,7 @@
 #include "blake2b_dev.h"
 #include "launch.h"
 
-// Register budget: the default (130 VGPRs → 3 waves/SIMD).  Forcing 4 waves/SIMD (≤128 VGPRs) was measured
+// Register budget: the default (148 VGPRs as a looping kernel, 130 before → 3 waves/SIMD either way).  Forcing 4 waves/SIMD (≤128 VGPRs) was measured
 // and is not faster (2.06 vs 2.10-2.15 TB/s at 4 M × 1 KiB): the VALU pipe is already ≈85-95 % busy.
 #ifndef IPCFP_K1_WAVES
 #define IPCFP_K1_WAVES 1
@@ -65,36 +65,42 @@ __device__ __forceinline__ void hash_block(const uint8_t* __restrict__ arena, ui
 
 // K1's per-lane metadata (K1Meta, witness_dev.h) is stored in SCHEDULE order so a wavefront reads it coalesced.
 
+// A RESIDENT grid: a workgroup of 256 threads — one wavefront per SIMD of a CU — takes the tiles
+// blockIdx.x, blockIdx.x + gridDim.x, … of 256 consecutive schedule entries.  The schedule is longest first, so the
+// static interleave hands every workgroup the same mix of lengths; no workgroup reads what another one writes.
 __global__ __launch_bounds__(256, IPCFP_K1_WAVES) void k_blake2b256_cid(const uint8_t* __restrict__ arena,
                                                        const K1Meta* __restrict__ meta,
                                                        const uint8_t* __restrict__ sched_cids40, uint32_t n,
                                                        uint32_t* __restrict__ ok_bits,
                                                        uint8_t* __restrict__ status,
                                                        unsigned long long* __restrict__ counters) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n) return;
-    const K1Meta mt = meta[t];
-    const uint32_t i = mt.id;
+    const uint32_t n_tiles = (n >> 8) + ((n & 255u) != 0u);
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t t = tile * 256u + threadIdx.x;
+        if (t >= n) continue;
+        const K1Meta mt = meta[t];
+        const uint32_t i = mt.id;
 
-    // claimed CID: 01 <codec> a0 e4 02 20 ‖ digest[32] ‖ 00 00   (40-byte slot)
-    const uint64_t* cw = reinterpret_cast<const uint64_t*>(sched_cids40 + 40ull * t);
-    const uint64_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3], w4 = cw[4];
-    const bool is_b2b = ((w0 & 0x0000FFFFFFFF00FFULL) == 0x00002002e4a00001ULL) && ((w0 & 0x8000ULL) == 0) &&
-                        ((w4 >> 48) == 0);
-    uint8_t st = IPCFP_CID_UNCHECKED;
-    if (is_b2b) {
-        uint64_t h[8];
-        hash_block(arena, mt.off, mt.len, h);
-        const uint64_t e0 = (w0 >> 48) | (w1 << 16);
-        const uint64_t e1 = (w1 >> 48) | (w2 << 16);
-        const uint64_t e2 = (w2 >> 48) | (w3 << 16);
-        const uint64_t e3 = (w3 >> 48) | (w4 << 16);
-        const bool ok = ((h[0] ^ e0) | (h[1] ^ e1) | (h[2] ^ e2) | (h[3] ^ e3)) == 0;
-        st = ok ? IPCFP_CID_OK : IPCFP_CID_MISMATCH;
-        if (ok) atomicOr(&ok_bits[i >> 5], 1u << (i & 31));
-        else atomicAdd(&counters[0], 1ull);
+        // claimed CID: 01 <codec> a0 e4 02 20 ‖ digest[32] ‖ 00 00   (40-byte slot)
+        const uint64_t* cw = reinterpret_cast<const uint64_t*>(sched_cids40 + 40ull * t);
+        const uint64_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3], w4 = cw[4];
+        const bool is_b2b = ((w0 & 0x0000FFFFFFFF00FFULL) == 0x00002002e4a00001ULL) && ((w0 & 0x8000ULL) == 0) &&
+                            ((w4 >> 48) == 0);
+        uint8_t st = IPCFP_CID_UNCHECKED;
+        if (is_b2b) {
+            uint64_t h[8];
+            hash_block(arena, mt.off, mt.len, h);
+            const uint64_t e0 = (w0 >> 48) | (w1 << 16);
+            const uint64_t e1 = (w1 >> 48) | (w2 << 16);
+            const uint64_t e2 = (w2 >> 48) | (w3 << 16);
+            const uint64_t e3 = (w3 >> 48) | (w4 << 16);
+            const bool ok = ((h[0] ^ e0) | (h[1] ^ e1) | (h[2] ^ e2) | (h[3] ^ e3)) == 0;
+            st = ok ? IPCFP_CID_OK : IPCFP_CID_MISMATCH;
+            if (ok) atomicOr(&ok_bits[i >> 5], 1u << (i & 31));
+            else atomicAdd(&counters[0], 1ull);
+        }
+        status[i] = st;
     }
-    status[i] = st;
 }
 
 // Raw digests (ipcfp_blake2b256_batch): out32[id] = Blake2b-256(block).
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(256) void k_chunk_scatter(const uint32_t* __restric
 }
 
 // ------------------------------ launchers -----------------------------------
-constexpr uint32_t kK1Wg = 64;  // threads per workgroup of the two hash kernels (64-256 measured: profiles/r01_k1_tune_first.log)
+constexpr uint32_t kK1Wg = 64;  // threads per workgroup of k_blake2b256_raw (64-256 measured: profiles/r01_k1_tune_first.log)
 
 int launch_chunk_order(ipcfp_ctx* ctx, const uint32_t* len_d, uint32_t n, uint32_t* bins_d /*256*/,
                        uint32_t* order_d) {
@@ -281,7 +287,8 @@ int launch_blake2b256_cid(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta
     if (n == 0) return IPCFP_OK;
     {
         ProfileScope prof(ctx, IPCFP_K_BLAKE2B_CID, s);
-        hipLaunchKernelGGL(k_blake2b256_cid, dim3(div_up(n, kK1Wg)), dim3(kK1Wg), 0, s, arena, static_cast<const K1Meta*>(meta),
+        const uint32_t grid = resident_grid(div_up(n, 256u), ctx->k1_resident, ctx->props.multiProcessorCount);
+        hipLaunchKernelGGL(k_blake2b256_cid, dim3(grid), dim3(256), 0, s, arena, static_cast<const K1Meta*>(meta),
                            sched_cids40, n, ok_bits, status, counters);
     }
     IPCFP_HIP(ctx, hipGetLastError());

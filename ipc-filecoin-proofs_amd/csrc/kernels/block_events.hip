@@ -157,19 +157,27 @@ __device__ __forceinline__ void block_events_parse(Rd& r, bool mine, uint64_t ar
     }
 }
 
+// A RESIDENT grid: a workgroup takes the tiles blockIdx.x, blockIdx.x + gridDim.x, … of 256 consecutive
+// schedule entries.  The loop bound is the same for all 256 threads, so all 64 lanes of a wavefront reach the wave-level
+// reservation of every iteration; the pool partition follows the LOGICAL wavefront number (tile * 4 + wave), so it does
+// not depend on the grid.  A lane's LDS slot is its own, and Rd::init invalidates it: no barrier between two tiles.
 __global__ __launch_bounds__(256, 4) void k_block_events(const uint8_t* __restrict__ arena, const K1Meta* __restrict__ meta, uint32_t n,
                                                          ScanParams sp, int count_matches, BlockRec* __restrict__ brecs,
                                                          EventRec* __restrict__ erecs, uint32_t cap_events,
                                                          uint32_t* __restrict__ pool_used) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = s < n;
-    K1Meta m{0, 0, kNoBlock};
-    if (live) m = meta[s];
-    BlockRec br{RK_WALK, 0, 0};
-    Rd r;
-    r.init(arena + m.off, live ? m.len : 0u);
-    block_events_parse(r, live, m.off, sp, count_matches, erecs, cap_events, pool_parts(n), pool_used, s >> 6, threadIdx.x & 63u, br);
-    if (live) brecs[m.id] = br;
+    const uint32_t n_tiles = (n >> 8) + ((n & 255u) != 0u), n_parts = pool_parts(n);
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t s = tile * 256u + threadIdx.x;
+        const bool live = s < n;
+        K1Meta m{0, 0, kNoBlock};
+        if (live) m = meta[s];
+        BlockRec br{RK_WALK, 0, 0};
+        Rd r;
+        r.init(arena + m.off, live ? m.len : 0u);
+        block_events_parse(r, live, m.off, sp, count_matches, erecs, cap_events, n_parts, pool_used, tile * 4u + (threadIdx.x >> 6),
+                           threadIdx.x & 63u, br);
+        if (live) brecs[m.id] = br;
+    }
 }
 
 int launch_block_events(ipcfp_ctx* ctx, hipStream_t stream, const uint8_t* arena, const void* meta_d, uint32_t n,
@@ -180,7 +188,8 @@ int launch_block_events(ipcfp_ctx* ctx, hipStream_t stream, const uint8_t* arena
     if (filter) sp = ScanParams{*filter, actor, has_actor ? 1u : 0u, 0};
     {
         ProfileScope prof(ctx, IPCFP_K_EVENT_SCAN, stream);
-        hipLaunchKernelGGL(k_block_events, dim3(div_up(n, 256)), dim3(256), 0, stream, arena, static_cast<const K1Meta*>(meta_d), n, sp,
+        const uint32_t grid = resident_grid(div_up(n, 256u), ctx->parse_resident, ctx->props.multiProcessorCount);
+        hipLaunchKernelGGL(k_block_events, dim3(grid), dim3(256), 0, stream, arena, static_cast<const K1Meta*>(meta_d), n, sp,
                            filter ? 1 : 0, brecs_d, erecs_d, cap_events, pool_used_d);
     }
     IPCFP_HIP(ctx, hipGetLastError());
