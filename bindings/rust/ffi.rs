@@ -438,6 +438,29 @@ impl Witness<'_> {
         statuses_to_result(&st)
     }
 
+    /// `serde_json::to_string(&UnifiedProofBundle { storage_proofs, event_proofs, blocks })` where `blocks` are the listed
+    /// blocks of this witness (`None`: every block in id order): the claim strings are written on the host, every
+    /// `ProofBlock` — base64 included — on the device out of the resident arena.  A sizing call, then the writing call.
+    pub fn bundle_to_json(&self, storage_proofs: &[StorageProof], event_proofs: &[EventProof], block_ids: Option<&[u32]>) -> Result<String> {
+        let keep_s: Vec<_> = storage_proofs.iter().map(CStorageProof::new).collect();  // own the C strings
+        let keep_e: Vec<_> = event_proofs.iter().map(CEventProof::new).collect();
+        let raw_s: Vec<ipcfp_storage_proof_t> = keep_s.iter().map(|k| k.raw()).collect();
+        let raw_e: Vec<ipcfp_event_proof_t> = keep_e.iter().map(|k| k.raw()).collect();
+        let (ids, n_ids) = match block_ids {
+            Some(v) => (v.as_ptr(), v.len() as u64),
+            None => (std::ptr::null(), unsafe { ipcfp_witness_block_count(self.raw()) }),
+        };
+        let mut len = 0u64;
+        let rc = unsafe { ipcfp_bundle_write_json(self.eng.ctx, self.raw(), raw_s.as_ptr(), raw_s.len() as u64, raw_e.as_ptr(), raw_e.len() as u64,
+                                                  ids, n_ids, std::ptr::null_mut(), 0, &mut len) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_bundle_write_json", rc)); }
+        let mut text = vec![0u8; len as usize];
+        let rc = unsafe { ipcfp_bundle_write_json(self.eng.ctx, self.raw(), raw_s.as_ptr(), raw_s.len() as u64, raw_e.as_ptr(), raw_e.len() as u64,
+                                                  ids, n_ids, text.as_mut_ptr() as *mut c_char, len, &mut len) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_bundle_write_json", rc)); }
+        String::from_utf8(text).map_err(|e| anyhow!("ipcfp_bundle_write_json: {e}"))
+    }
+
     /// drop-in for `verify_storage_proof` over all storage proofs of a bundle (src/proofs/storage/verifier.rs:24-63;
     /// the loop of src/proofs/verifier.rs:19-28 — the witness is NOT rebuilt per proof).
     pub fn verify_storage_proof(&self, proofs: &[StorageProof], trust: &ipcfp_trust_policy_t) -> Result<Vec<bool>> {

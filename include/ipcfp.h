@@ -944,6 +944,29 @@ int ipcfp_verify_proof_bundle(ipcfp_ctx_t* ctx, ipcfp_bundle_t* b, const ipcfp_t
                               const ipcfp_event_filter_t* filter, ipcfp_status_t* storage_status,
                               ipcfp_status_t* event_status);
 
+/* The WRITE direction: the text `serde_json::to_string(&UnifiedProofBundle)` produces (compact, fields in declaration
+ * order, `cid` as the array of decimal bytes the parser reads, `data` as standard base64 with '=' padding; strings
+ * escaped by serde_json's rule: \" \\ \b \t \n \f \r, \u00xx for the other bytes below 0x20, everything else verbatim).
+ * Both calls: *len always receives the exact byte length of the text (no NUL, no newline); out == NULL with cap == 0
+ * is the sizing call (IPCFP_OK, nothing written); cap < *len is IPCFP_E_INVALID and nothing is written.  A claim string
+ * that is NULL or not well-formed UTF-8 (a Rust `String` cannot hold it) is IPCFP_E_INVALID.
+ *
+ * host only, no context: `{"storage_proofs":[…],"event_proofs":[…],"blocks":[` — the head of the text, up to and
+ * including the '[' of blocks */
+int ipcfp_bundle_write_claims_json(const ipcfp_storage_proof_t* storage, uint64_t n_storage,
+                                   const ipcfp_event_proof_t* events, uint64_t n_events,
+                                   char* out, uint64_t cap, uint64_t* len);
+/* the whole bundle: head + one ProofBlock per listed block of `w` (base64 written on the device) + `]}`.
+ * block_ids == NULL: every block of w in id order (n_blocks must then equal the witness's count); a repeated id writes
+ * the block again.  All or nothing; ipcfp_last_error names the lowest offending POSITION of block_ids: an id that is not
+ * a block of w and a CID slot that is not one well-formed CID are IPCFP_E_INVALID, a folded slot (a CID longer than
+ * IPCFP_CID_SLOT, whose bytes the witness does not keep) is IPCFP_E_UNSUPPORTED. */
+int ipcfp_bundle_write_json(ipcfp_ctx_t* ctx, ipcfp_witness_t* w,
+                            const ipcfp_storage_proof_t* storage, uint64_t n_storage,
+                            const ipcfp_event_proof_t* events, uint64_t n_events,
+                            const uint32_t* block_ids, uint64_t n_blocks,
+                            char* out, uint64_t cap, uint64_t* len);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -32,6 +32,7 @@ __all__ = [
     "Witness",
     "Bundle",
     "bundle_check_json",
+    "bundle_claims_json",
     "pack_event_proofs",
     "pack_storage_proofs",
     "GEN_STORAGE_DTYPE",
@@ -365,6 +366,8 @@ def load_library() -> C.CDLL:
         "ipcfp_bundle_event_proofs": (vp, [vp]),
         "ipcfp_bundle_storage_proofs": (vp, [vp]),
         "ipcfp_verify_proof_bundle": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ipcfp_bundle_write_claims_json": (i32, [vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
+        "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -957,6 +960,29 @@ def bundle_check_json(text: bytes, flags: int = 0):
     return rc == 0, int(ns.value), int(ne.value), int(nb.value), err.value.decode(errors="replace")
 
 
+def _claims_ptr(arr):
+    """A ctypes array of claim structs, an address, or None → c_void_p"""
+    if arr is None or isinstance(arr, (int, C.c_void_p)):
+        return arr
+    return C.cast(arr, C.c_void_p)
+
+
+def bundle_claims_json(storage_arr, n_storage: int, event_arr, n_events: int) -> bytes:
+    """The head of a bundle's JSON text, `{"storage_proofs":[…],"event_proofs":[…],"blocks":[`, as serde_json writes it
+    (ipcfp_bundle_write_claims_json: host only, no engine).  The arrays are ctypes arrays of the ipcfp.h claim structs."""
+    lib = load_library()
+    sp, ep = _claims_ptr(storage_arr), _claims_ptr(event_arr)
+    n = C.c_uint64()
+    rc = lib.ipcfp_bundle_write_claims_json(sp, n_storage, ep, n_events, None, 0, C.byref(n))
+    if rc != 0:
+        raise EngineError(f"bundle_write_claims_json: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+    buf = C.create_string_buffer(max(int(n.value), 1))
+    rc = lib.ipcfp_bundle_write_claims_json(sp, n_storage, ep, n_events, C.cast(buf, C.c_void_p), n.value, C.byref(n))
+    if rc != 0:
+        raise EngineError(f"bundle_write_claims_json: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+    return buf.raw[: int(n.value)]
+
+
 class Bundle:
     """A parsed `UnifiedProofBundle` JSON (``ipcfp_bundle_t``): witness in HBM + the claim structs."""
 
@@ -984,6 +1010,11 @@ class Bundle:
             self.eng.h, self.h, C.cast(C.pointer(trust), C.c_void_p) if trust is not None else None,
             C.cast(C.pointer(filt), C.c_void_p) if filt is not None else None, _p(ss), _p(es)), "verify_proof_bundle")
         return ss[: self.n_storage], es[: self.n_events]
+
+    def to_json(self) -> bytes:
+        """The bundle back as its JSON wire form: its own claim structs and every block of its witness in id order."""
+        return self.witness.write_bundle_json(self.lib.ipcfp_bundle_storage_proofs(self.h), self.n_storage,
+                                              self.lib.ipcfp_bundle_event_proofs(self.h), self.n_events)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1049,6 +1080,22 @@ class Witness:
     @property
     def block_count(self) -> int:
         return int(self.lib.ipcfp_witness_block_count(self.h))
+
+    def write_bundle_json(self, storage_ptr, n_storage: int, event_ptr, n_events: int, block_ids=None) -> bytes:
+        """`serde_json::to_string(&UnifiedProofBundle)` of the given claims (ctypes arrays of the ipcfp.h structs, or
+        addresses) and the listed blocks of this witness (None: every block in id order); base64 on the device."""
+        sp, ep = _claims_ptr(storage_ptr), _claims_ptr(event_ptr)
+        if block_ids is None:
+            ids, nb = None, self.n
+        else:
+            ids = np.ascontiguousarray(block_ids, dtype=np.uint32)
+            nb = len(ids)
+        n = C.c_uint64()
+        args = (self.eng.h, self.h, sp, n_storage, ep, n_events, _p(ids), nb)
+        self.eng._check(self.lib.ipcfp_bundle_write_json(*args, None, 0, C.byref(n)), "bundle_write_json")
+        out = np.empty(int(n.value), dtype=np.uint8)
+        self.eng._check(self.lib.ipcfp_bundle_write_json(*args, _p(out), out.size, C.byref(n)), "bundle_write_json")
+        return out.tobytes()
 
     def verify_cids(self):
         """K1.  Returns (status u8[n], n_bad)."""

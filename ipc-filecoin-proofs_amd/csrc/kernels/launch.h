@@ -113,6 +113,8 @@ int launch_expand_claims(ipcfp_ctx* ctx, const void* compact_d, uint32_t n, cons
 // --- scan.hip ---
 int launch_scan_u32(ipcfp_ctx* ctx, const uint32_t* in_d, uint32_t n, uint32_t* out_d, uint64_t* total_d,
                     uint64_t* scratch_d);
+int launch_scan_u64(ipcfp_ctx* ctx, const uint64_t* in_d, uint32_t n, uint64_t* out_d, uint64_t* total_d,
+                    uint64_t* scratch_d);
 
 // --- verify_events.hip ---
 struct TipsetCtxDev;
@@ -198,6 +200,19 @@ int launch_base64_decode(ipcfp_ctx* ctx, const uint8_t* text_d, const void* span
 
 int launch_parse_cid_arrays(ipcfp_ctx* ctx, const uint8_t* text_d, const void* spans_d, uint32_t n, uint8_t* cids_d,
                             unsigned long long* first_bad_d);
+
+// --- base64_encode.hip --- the `blocks` part of a bundle's JSON text out of the witness (host/bundle_write.cpp)
+// per list position (ids_d nullable: the identity list): EncPos records (16 B each), text sizes and their exclusive prefix,
+// the 16-character unit prefix; totals_d = [text bytes, units]; *first_bad_d = min over (position << 2 | code),
+// code 1: id out of range, 2: folded CID slot, 3: slot is not one CID + zero padding; scratch_d: 2·(div_up(n,1024)+1) u64
+int launch_bundle_block_sizes(ipcfp_ctx* ctx, const uint32_t* ids_d, uint32_t n, uint32_t n_witness, const uint64_t* off_d,
+                              const uint32_t* len_d, const uint8_t* cids_d, void* pos_d, uint64_t* size_d, uint32_t* units_d,
+                              uint64_t* text_off_d, uint32_t* unit0_d, uint64_t* totals_d, uint64_t* scratch_d,
+                              unsigned long long* first_bad_d);
+// the frames of every position and the base64 bodies into text_d (totals_d[0] bytes)
+int launch_bundle_write_text(ipcfp_ctx* ctx, const uint32_t* ids_d, uint32_t n, const uint8_t* arena_d, const uint8_t* cids_d,
+                             const void* pos_d, const uint64_t* text_off_d, const uint32_t* unit0_d, uint32_t n_units,
+                             uint8_t* text_d);
 
 // --- generate.hip ---
 int launch_generate_storage(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& child, const void* specs_d, uint32_t n,

@@ -114,4 +114,62 @@ int launch_scan_u32(ipcfp_ctx* ctx, const uint32_t* in_d, uint32_t n, uint32_t* 
     return IPCFP_OK;
 }
 
+// ---- the same over 64-bit items with 64-bit results (text offsets of a bundle: past 4 GB long before anything else) ----
+__global__ __launch_bounds__(256) void k_scan_tile_sums_u64(const uint64_t* __restrict__ in, uint32_t n,
+                                                            uint64_t* __restrict__ tile_sums) {
+    __shared__ uint64_t smem[17];
+    const uint32_t base = blockIdx.x * 1024u + threadIdx.x * 4u;
+    uint64_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (base + k < n) s += in[base + k];
+    uint64_t total;
+    (void)block_exclusive_scan(s, smem, &total);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// tile_base == nullptr: the one tile is the whole input, and the total goes to *total_out
+__global__ __launch_bounds__(256) void k_scan_apply_u64(const uint64_t* __restrict__ in, uint32_t n,
+                                                        const uint64_t* __restrict__ tile_base, uint64_t* __restrict__ out,
+                                                        uint64_t* __restrict__ total_out) {
+    __shared__ uint64_t smem[17];
+    const uint32_t base = blockIdx.x * 1024u + threadIdx.x * 4u;
+    uint64_t r[4];
+    uint64_t s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        r[k] = (base + k < n) ? in[base + k] : 0;
+        s += r[k];
+    }
+    uint64_t total;
+    uint64_t ex = block_exclusive_scan(s, smem, &total) + (tile_base ? tile_base[blockIdx.x] : 0ull);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < n) out[base + k] = ex;
+        ex += r[k];
+    }
+    if (!tile_base && threadIdx.x == 0) *total_out = total;
+}
+
+// out[i] = sum of in[0..i) over u64; *total_d = sum of all.  scratch_d must hold div_up(n,1024)+1 u64.
+int launch_scan_u64(ipcfp_ctx* ctx, const uint64_t* in_d, uint32_t n, uint64_t* out_d, uint64_t* total_d,
+                    uint64_t* scratch_d) {
+    if (n == 0) {
+        IPCFP_HIP(ctx, hipMemsetAsync(total_d, 0, sizeof(uint64_t), ctx->stream));
+        return IPCFP_OK;
+    }
+    if (n <= 1024) {
+        hipLaunchKernelGGL(k_scan_apply_u64, dim3(1), dim3(256), 0, ctx->stream, in_d, n, static_cast<const uint64_t*>(nullptr),
+                           out_d, total_d);
+        IPCFP_HIP(ctx, hipGetLastError());
+        return IPCFP_OK;
+    }
+    const uint32_t ntiles = div_up(n, 1024);
+    hipLaunchKernelGGL(k_scan_tile_sums_u64, dim3(ntiles), dim3(256), 0, ctx->stream, in_d, n, scratch_d);
+    hipLaunchKernelGGL(k_scan_tiles_u64, dim3(1), dim3(256), 0, ctx->stream, scratch_d, ntiles, total_d);
+    hipLaunchKernelGGL(k_scan_apply_u64, dim3(ntiles), dim3(256), 0, ctx->stream, in_d, n, scratch_d, out_d, total_d);
+    IPCFP_HIP(ctx, hipGetLastError());
+    return IPCFP_OK;
+}
+
 }  // namespace ipcfp
