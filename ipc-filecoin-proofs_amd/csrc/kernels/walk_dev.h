@@ -258,12 +258,14 @@ __device__ __forceinline__ uint32_t amt_load_get(const WitnessView& w, const Cid
 // Hamt::load_with_bit_width(root, bw).get(key): TRUE ⇒ loc set; NOT_FOUND; ERR_*.
 __device__ __forceinline__ uint32_t hamt_get(const WitnessView& w, const CidKey& root, uint32_t bit_width, int vkind,
                                              const uint8_t* key, uint32_t key_len, ValueLoc& loc) {
-    if (bit_width < 1 || bit_width > 8) return IPCFP_ST_ERR_DECODE;
     uint32_t h[8];
     sha256::hash_bytes(key, key_len, h);
     uint32_t consumed = 0;
     uint32_t block = witness_find(w, root);
-    if (block == kNoBlock) return IPCFP_ST_ERR_MISSING_BLOCK;
+    if (block == kNoBlock) return IPCFP_ST_ERR_MISSING_BLOCK;  // `load_with_bit_width` fetches the root whatever the width
+    // a width HashBits::next refuses is an Err of the get; a root that does not decode is the same status, so the order of
+    // the two does not show
+    if (bit_width < 1 || bit_width > 8) return IPCFP_ST_ERR_DECODE;
     for (;;) {
         Rd r = open_block(w, block);
         // HashBits::next happens after the node is decoded; compute idx first only when bits remain
@@ -442,13 +444,13 @@ __device__ __forceinline__ uint32_t table_hamt_get(const WitnessView& w, const H
     // `root_block` / `root_children` (optional): the root's block id and the blocks behind its pointers as SOMEBODY ELSE has
     // already resolved them (kNoBlock where not: the link is then read and looked up here) — the 256 storage proofs of one
     // contract all start at the same root and step through one of its 32 links (verify_storage.hip k_storage_run_children).
+    uint32_t block = root_block != kNoBlock ? root_block : witness_find(w, root);
+    if (block == kNoBlock) return IPCFP_ST_ERR_MISSING_BLOCK;  // the root is fetched whatever the width (see hamt_get)
     if (bit_width < 1 || bit_width > 8) return IPCFP_ST_ERR_DECODE;
     uint32_t h[8];
     if (key_words && key_len == 32) sha256::hash32_words(key_words, h);
     else sha256::hash_bytes(key, key_len, h);
     uint32_t consumed = 0;
-    uint32_t block = root_block != kNoBlock ? root_block : witness_find(w, root);
-    if (block == kNoBlock) return IPCFP_ST_ERR_MISSING_BLOCK;
     for (;;) {
         const HamtNodeRec* rec = table + block;
         const uint4 rh = *reinterpret_cast<const uint4*>(rec);  // the record's first 16 bytes in one read

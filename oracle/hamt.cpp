@@ -70,11 +70,13 @@ HNode read_hnode(const Bytes& raw, const ValueChecker& check) {
 
 bool hamt_get(const Blockstore& bs, const Cid& root, uint32_t bit_width, const uint8_t* key, size_t key_len,
               const ValueChecker& check, ValueLoc& loc) {
-    if (bit_width < 1 || bit_width > 8) decode_err("HAMT bit width out of the supported range");
     uint8_t h[32];
     sha256(key, key_len, h);
     uint32_t consumed = 0;
+    // storage/decode.rs:79-81: `load_with_bit_width(&root, ..)?` fetches the root first, whatever the width; the width is
+    // refused by the get that follows (a root that does not decode gives the same status, so that order does not show)
     const Bytes* raw = &must_get(bs, root, "HAMT root");
+    if (bit_width < 1 || bit_width > 8) decode_err("HAMT bit width out of the supported range");
     for (;;) {
         HNode nd = read_hnode(*raw, check);
         // HashBits::next(bit_width)

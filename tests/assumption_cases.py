@@ -60,3 +60,76 @@ CASES = {
     "receipt_with_a_fifth_field_is_rejected": lambda: _case(_leaf_root(head(4, 5) + uint(0) + bstr(b"") + uint(1) + b"\xf6" + uint(0)), "receipt", 0, ERR_DECODE),
     "receipt_exit_code_above_u32_is_rejected": lambda: _case(_leaf_root(head(4, 4) + uint(1 << 32) + bstr(b"") + uint(1) + b"\xf6"), "receipt", 0, ERR_DECODE),
 }
+
+
+# --- serde's derive and fvm_ipld_hamt, carried by a storage chain (tests/storage_chain_cases.py `chain`) -------------------
+# Each case: name → callable → (store, claim fields, expected status of verify_storage_proof).  tests/pystorage.py names each
+# assumption with a constant and makes the SAME choice the oracle and the engine were written to make: on these points the
+# three are one judge, and a case here pins what they do, it does not prove the crate does it.  tests/test_storage_chain.py
+# holds pystorage and the oracle to the table, tests/test_gpu_storage_chain.py every route of the engine;
+# tests/storage_chain_cases.py takes the cases into its own table, so they also run merged into one witness.
+def _sc():
+    import storage_chain_cases as sc
+
+    return sc
+
+
+def _storage_case(root_block, slot: bytes, value: bytes, expect: int, parts=False):
+    """root_block: the contract-state root's bytes, or callable(store) → bytes"""
+    import hashlib
+
+    salt = int.from_bytes(hashlib.sha256(slot + value + bytes([expect])).digest()[:3], "big")
+    store, claim, made = _sc().chain(root_block if callable(root_block) else (lambda st: root_block), slot, value, salt=salt)
+    return (store, claim, expect, made["dropped"]) if parts else (store, claim, expect)
+
+
+def _bucket_node(keys_and_bytes):
+    """a width-5 root node with ONE bucket at index 17 holding the pairs as given (value: Vec<u8>)"""
+    sc = _sc()
+    return sc.node(1 << 17, [sc.bucket([(k, sc.vec(v)) for k, v in keys_and_bytes])])
+
+
+def _keys_at_17(n):
+    sc = _sc()
+    return sorted(sc.slot_with_index(17, k) for k in range(n))
+
+
+def _b1_saying(width_said):
+    """B1 `[root, bitwidth]` over a tree built at width 5"""
+    sc = _sc()
+    return lambda st: array([link(sc.pyhamt.build_hamt(st, sc.hamt_items(sc.MANY), 5)), uint(width_said)])
+
+
+_SLOT, _VALUE = bytes(range(32)), b"\x2a"
+_PAIRS = array([array([bstr(_SLOT), bstr(_VALUE)])])
+_B01 = array([bstr(b"\x01"), array([])])  # `[h'01', []]`
+STORAGE_CASES = {
+    # STRUCT_FROM_ARRAY_IS_REJECTED.  A serde-derived struct (`SmallMap`, `MapStruct`: storage/decode.rs:10-13,28-32) is read
+    # from a CBOR MAP only.  Its fields offered as an ARRAY `[v]` — serde's derive has a visit_seq that would take them — are a
+    # decode error of that attempt: pystorage, the oracle and the engine all refuse it, and nothing later fits an array of 1
+    # (at C it is no HAMT node), so the call is ERR_DECODE where an accepting decoder would answer TRUE.
+    "struct_offered_as_an_array_is_rejected": lambda **o: _storage_case(array([_PAIRS]), _SLOT, _VALUE, ERR_DECODE, **o),
+    "the_same_struct_as_a_map_is_found": lambda **o: _storage_case(head(5, 1) + head(3, 1) + b"v" + _PAIRS, _SLOT, _VALUE, TRUE, **o),
+    # … and inside A2: `[params, [v]]` is then an A1 whose list holds a non-map — no attempt takes it; at C the one "pointer" is
+    # a bucket whose value is a byte string, no Vec<u8>
+    "struct_offered_as_an_array_inside_a2_is_rejected": lambda **o: _storage_case(array([bstr(b""), array([_PAIRS])]), _SLOT, _VALUE, ERR_DECODE, **o),
+    # HAMT_POINTER_COUNT_IS_CHECKED_WHEN_INDEXED.  `[h'01', []]` decodes as an A1 with an empty list, falls through
+    # (storage/decode.rs:47) and is, at C, a node whose bitfield names a pointer it does not have.  All three compare
+    # popcount and pointer list only where a get indexes the list: an Err for a key that lands on bit 0, a clear bit — zero,
+    # TRUE — for any other key.  A crate that compares them when it DECODES the node gives ERR_DECODE for both, as
+    # the AMT does (amt_value_count_must_match_the_bitmap above); flip the second case then.
+    "a1_bitfield_01_empty_list_key_on_bit_0": lambda **o: _storage_case(_B01, _sc().slot_with_index(0), b"", ERR_DECODE, **o),
+    "a1_bitfield_01_empty_list_key_on_bit_9": lambda **o: _storage_case(_B01, _sc().slot_with_index(9), b"", TRUE, **o),
+    # HAMT_BUCKET_SIZE_AND_ORDER_ARE_NOT_CHECKED_ON_READ.  SURVEY.md A.6 gives the bucket as "≤ 3, sorted by key" — what a
+    # writer produces — and the get as a linear search.  All three search the bucket as it stands; a crate that enforces either
+    # property on read gives ERR_DECODE for these two.
+    "c_bucket_of_4_fourth_key": lambda **o: _storage_case(_bucket_node([(k, bytes([i + 1])) for i, k in enumerate(_keys_at_17(4))]),
+                                                          _keys_at_17(4)[3], b"\x04", TRUE, **o),
+    "c_bucket_unsorted": lambda **o: _storage_case(_bucket_node([(_keys_at_17(3)[i], bytes([i + 1])) for i in (2, 0, 1)]),
+                                                   _keys_at_17(3)[0], b"\x01", TRUE, **o),
+    # HAMT_BIT_WIDTH_OUTSIDE_1_TO_8_IS_AN_ERR_OF_THE_GET.  `load_with_bit_width` takes any u32; all three report a width of 0 or
+    # of more than 8 as ERR_DECODE — the Err of `HashBits::next` — once the root is loaded.  (That the root is FETCHED first
+    # is the reference's text, storage/decode.rs:79-80, and no assumption: storage_chain_cases b1_bit_width_0_and_inner_root_absent.)
+    "b1_bit_width_0": lambda **o: _storage_case(_b1_saying(0), _sc().S[0], _sc().VAL[0], ERR_DECODE, **o),
+    "b1_bit_width_9": lambda **o: _storage_case(_b1_saying(9), _sc().S[0], _sc().VAL[0], ERR_DECODE, **o),
+}
