@@ -148,7 +148,8 @@ int ipcfp_ctx_sync(ipcfp_ctx_t* ctx);
  *   "hamt_levels"  -1 default (ipcfp_hamt_get*: level by level for batches of >= 1024 queries), 0 per-query walker only,
  *                  k > 0 exactly k levels whatever the batch size
  *   "hamt_coop"    0: the level path decodes ActorState nodes with one lane each instead of sixteen
- *   "hamt_table"   1: tabulate every block of the witness as a HAMT node first
+ *   "hamt_table"   ipcfp_hamt_get*: 1 answers from the per-call node table, made for every block of the witness first (the
+ *                  table the storage proofs use); ipcfp_verify_storage_proofs: 0 one lane per claim, no table
  *   "fast_verify"  0: verify_event_proof never takes the route without mid-call synchronisation
  *   "k1_resident", "parse_resident"   the grids of the CID check and of the block-order event parse: that many
  *                  workgroups of 256 threads per CU, each looping over tiles of 256 blocks; 0: one workgroup per tile.

@@ -44,7 +44,8 @@ static hipError_t grow(void*& p, size_t& cap, size_t need) {
 // K7 for a batch.  Default for a batch of ≥ 1024 queries: LEVEL BY LEVEL (kernels/hamt_levels.hip) — every node the batch
 // visits is decoded once, a query is SHA-256 + one record per level — with the per-query walker (k_hamt_get) behind it
 // for whatever that leaves pending.  Tuning key hamt_levels = 0: the walker alone (round 3's path; small batches take it
-// anyway).  Tuning key hamt_table = 1 (A/B measurements): tabulate EVERY block of the witness first (kernels/hamt_table.h).
+// anyway).  Tuning key hamt_table = 1: tabulate EVERY block of the witness first (kernels/hamt_table.h, the lane kernel at
+// any length) and answer from the table — the one route that drives table_hamt_get with every kind and bit width.
 int hamt_get_batch(ipcfp_ctx* ctx, ipcfp_witness* w, const CidKey& root, uint32_t bit_width, int vkind, const uint8_t* keys_d,
                    const uint32_t* key_off_d, const uint32_t* key_len_d, uint32_t n, uint8_t* status_d, void* loc_d) {
     const int forced_table = ctx->hamt_table, levels_mode = ctx->hamt_levels;
@@ -53,7 +54,7 @@ int hamt_get_batch(ipcfp_ctx* ctx, ipcfp_witness* w, const CidKey& root, uint32_
     const WitnessView view = witness_view(w);
     if (kbit && forced_table == 1) {
         IPCFP_HIP(ctx, grow(ctx->hamt_recs, ctx->hamt_recs_bytes, size_t(w->n) * sizeof(HamtNodeRec)));
-        int rc = launch_hamt_node_table(ctx, w->arena.p, w->k1_meta.p, uint32_t(w->n), kbit, ctx->hamt_recs);
+        int rc = launch_hamt_node_table_lane(ctx, w->arena.p, w->k1_meta.p, uint32_t(w->n), /*below_len=*/~0u, kbit, ctx->hamt_recs);
         if (rc) return rc;
         return launch_hamt_get_table(ctx, view, ctx->hamt_recs, root, bit_width, vkind, keys_d, key_off_d, key_len_d, n, status_d, loc_d);
     }

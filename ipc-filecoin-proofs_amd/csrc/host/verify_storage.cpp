@@ -109,10 +109,10 @@ static int verify_storage_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const Storage
         aux_guard.armed = true;
         hipStream_t saved = ctx->stream;
         ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
-        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kTableKinds, table.p);
+        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
         ctx->stream = saved;
     } else {
-        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kTableKinds, table.p);
+        rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
     }
     if (rc) return rc;
     if (wait_upload) {  // (the node table is on its way: from here on the kernels read claims)

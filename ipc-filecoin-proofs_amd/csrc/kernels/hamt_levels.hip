@@ -27,6 +27,7 @@
 #include "../common.h"
 #include "launch.h"
 #include "hamt_outline.h"
+#include "hamt_table_body.h"
 #include "walk_dev.h"
 
 namespace ipcfp {
@@ -168,60 +169,27 @@ __global__ __launch_bounds__(256) void k_hamt_lv_start(WitnessView w, CidKey roo
     }
 }
 
-// lane = one node of level `level`'s work list
+// The level parse's bucket-entry step (hamt_node_parse): `[key bytes, value]` with the value checked as the HAMT's one
+// value kind — an ActorState entry in its usual spelling from a handful of fetches (actor_entry_fast).
+struct HamtLevelEntry {
+    int vkind;
+    __device__ __forceinline__ void operator()(Rd& r, uint32_t&) const {
+        uint32_t ko, kl, vstart;
+        if (vkind == VK_ACTOR_STATE && actor_entry_fast(r, ko, kl, vstart)) return;
+        r.expect_array(2);
+        r.read_bytes(ko, kl);
+        check_value(r, vkind);
+    }
+};
+
+// lane = one node of level `level`'s work list (kinds_ok = status: the node was checked for the call's one value kind)
 __global__ __launch_bounds__(256, IPCFP_WALK_WAVES) void k_hamt_lv_parse(WitnessView w, HamtLevels L, uint32_t level, int vkind) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L.count[kHamtClasses * level]) return;
     const uint32_t block = L.work[level & 1u][0][i].x;
     HamtNodeRec* out = L.recs + block;
     Rd r = open_block(w, block);
-    uint32_t status = 0, std_links = 0, np32 = 0;
-    uint64_t bf = 0;
-    do {
-        r.expect_array(2);
-        uint32_t bo, bl;
-        r.read_bytes(bo, bl);
-        if (!r.ok() || bl > 8) break;
-        if (bl) {  // big-endian integer, leading zeros stripped: the last byte holds bits 0..7
-            const uint64_t v = r.peek64(bo);
-            bf = __builtin_bswap64(v) >> (64u - 8u * bl);
-        }
-        const uint64_t np = r.read_array();
-        if (!r.ok() || np > kHamtTablePointers) break;
-        np32 = uint32_t(np);
-        bool fits = true;
-        for (uint32_t p = 0; p < np32 && r.ok(); ++p) {
-            const uint32_t at = r.pos;
-            fits = fits && at <= 0xffffu;
-            out->ptr_off[p] = uint16_t(at);
-            const uint32_t b0 = r.peek();
-            if ((b0 >> 5) == 6) {
-                uint32_t o, l;
-                r.read_link(o, l);
-                if (r.ok() && l == 38 && o == at + 5) std_links |= 1u << p;  // (read_link's own fast path saw the standard form)
-            } else if ((b0 >> 5) == 4) {
-                const uint64_t nkv = r.read_array();
-                for (uint64_t k = 0; k < nkv && r.ok(); ++k) {
-                    uint32_t ko, kl, vstart;
-                    if (vkind == VK_ACTOR_STATE && actor_entry_fast(r, ko, kl, vstart)) continue;
-                    r.expect_array(2);
-                    r.read_bytes(ko, kl);
-                    check_value(r, vkind);
-                }
-            } else {
-                r.fail();
-            }
-        }
-        r.finish();
-        if (r.ok() && fits) status = 1;
-    } while (false);
-    // a standard link must really be one: l == 38 at at + 5 is also what the long way reports for that spelling only
-    out->status = uint8_t(status);
-    out->kinds_ok = uint8_t(status);
-    out->np = uint8_t(np32);
-    out->pad = 0;
-    out->std_links = std_links;
-    out->bitfield = bf;
+    hamt_rec_store(out, hamt_node_parse(r, out, 1u, HamtLevelEntry{vkind}));
 }
 
 // ---- the same for `Hamt<_, ActorState>` (the state tree: src/proofs/common/decode.rs:29-39), THIRTY-TWO LANES PER NODE ----
@@ -852,7 +820,8 @@ __global__ __launch_bounds__(256) void k_hamt_lv_advance_top(WitnessView w, Hamt
     }
 }
 
-// Scratch of one call: [cur n | hash 8n | 4 work lists of cap 16-byte entries | count 2 (levels + 2) | claimed words | 8 spare] u32 + child table + etab_of.
+// Scratch of one call: [cur n | hash 8n | 2 · kHamtClasses work lists of cap 16-byte entries | count kHamtClasses (levels + 2) | claimed words | 8 spare] u32
+// + child table + etab_of.
 size_t hamt_levels_scratch_words(uint32_t n, uint32_t n_blocks, uint32_t levels) {
     const size_t cap = n < n_blocks ? n : n_blocks;
     return size_t(n) * 9 + 4 + cap * 24 + 3 * size_t(levels + 2) + div_up(n_blocks, 32) + 8 + size_t(n_blocks) * kHamtTablePointers + size_t(n_blocks);

@@ -22,9 +22,11 @@
 namespace ipcfp {
 
 constexpr uint32_t kHamtTablePointers = 32;
-// The per-call node table is made by two kernels (hamt_table_lane.hip): blocks of at least this many bytes — the 4-5 KB
-// bucket nodes of a state tree — go to the 32-lane outline (hamt_levels.hip), shorter ones to one lane each; a long block
-// the outline does not take (it reads ActorState buckets only) gets its lane afterwards.
+// The storage call's node table is made by two kernels (hamt_table_lane.hip): blocks of at least this many bytes — the
+// 4-5 KB bucket nodes of a state tree — go to the 32-lane outline (hamt_levels.hip), shorter ones to one lane each; a long
+// block the outline does not take (it reads ActorState buckets only) gets its lane afterwards.  The table route of
+// ipcfp_hamt_get* gives every block to the lane kernel.  Both lane kernels run the ONE item-by-item parse of a node
+// (hamt_table_body.h hamt_node_parse), which the level-by-level walk's one-lane parse shares.
 constexpr uint32_t kHamtOutlineMinLen = 2048;
 enum : uint32_t { HK_ACTOR_STATE = 1u << 0, HK_VEC_U8 = 1u << 1, HK_ANY = 1u << 2 };
 

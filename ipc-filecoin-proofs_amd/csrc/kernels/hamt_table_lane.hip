@@ -1,6 +1,7 @@
 // csrc/kernels/hamt_table_lane.hip — the HAMT node table (hamt_table.h), one block per LANE in arena order, the reader
 // staging the 128 bytes it is about to read in the lane's LDS slot (cbor_dev.h IPCFP_LINE_STAGE) — the form that won for the
-// block-order event parse (block_events.hip), against the eight-lanes-per-block ring reader of hamt_table.hip.
+// block-order event parse (block_events.hip).  The storage call gives it the blocks below kHamtOutlineMinLen and the
+// 32-lane outline (hamt_levels.hip) the rest; the table route of ipcfp_hamt_get* gives it every block.
 #ifndef IPCFP_LINE_STAGE
 #define IPCFP_LINE_STAGE 2  // (a window the parse re-aims once per pointer and bucket entry: cbor_dev.h)
 #endif
@@ -14,26 +15,17 @@
 namespace ipcfp {
 
 __global__ __launch_bounds__(256, 4) void k_hamt_node_table_lane(const uint8_t* __restrict__ arena, const K1Meta* __restrict__ meta,
-                                                                 uint32_t n, uint32_t kinds, HamtNodeRec* __restrict__ recs) {
+                                                                 uint32_t n, uint32_t below_len, uint32_t kinds, HamtNodeRec* __restrict__ recs) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     bool live = s < n;
     K1Meta m{0, 0, 0};
     if (live) m = meta[s];
-    live = live && m.len < kHamtOutlineMinLen;  // (the longer blocks are the 32-lane outline's: launch_hamt_node_table)
+    live = live && m.len < below_len;  // (kHamtOutlineMinLen: the longer blocks are the 32-lane outline's; ~0: every block)
     HamtNodeRec* out = recs + m.id;
     Rd r;
-    r.init(arena + m.off, live ? m.len : 0u);
-    uint32_t status, kinds_ok, std_links, np32;
-    uint64_t bf;
-    hamt_node_parse(r, kinds, live, out, status, kinds_ok, std_links, np32, bf);
-    if (live) {
-        out->status = uint8_t(status);
-        out->kinds_ok = uint8_t(status ? kinds_ok : 0u);
-        out->np = uint8_t(np32);
-        out->pad = 0;
-        out->std_links = std_links;
-        out->bitfield = bf;
-    }
+    r.init(arena + m.off, live ? m.len : 0u);  // (length 0: hamt_node_parse stores nothing)
+    const HamtNodeFacts f = hamt_node_parse(r, out, hamt_table_kinds_all(kinds), HamtTableEntry{kinds});
+    if (live) hamt_rec_store(out, f);
 }
 
 // the blocks the outline takes, as a work list (schedule order is by length class, longest first: they are a prefix, found
@@ -63,17 +55,8 @@ __global__ __launch_bounds__(256, 4) void k_hamt_node_table_rest(WitnessView w, 
     HamtNodeRec* out = recs + id;
     Rd r;
     r.init(w.arena + (live ? w.off[id] : 0ull), live ? w.len[id] : 0u);
-    uint32_t status, kinds_ok, std_links, np32;
-    uint64_t bf;
-    hamt_node_parse(r, kinds, live, out, status, kinds_ok, std_links, np32, bf);
-    if (live) {
-        out->status = uint8_t(status);
-        out->kinds_ok = uint8_t(status ? kinds_ok : 0u);
-        out->np = uint8_t(np32);
-        out->pad = 0;
-        out->std_links = std_links;
-        out->bitfield = bf;
-    }
+    const HamtNodeFacts f = hamt_node_parse(r, out, hamt_table_kinds_all(kinds), HamtTableEntry{kinds});
+    if (live) hamt_rec_store(out, f);
 }
 
 int launch_hamt_node_table_rest(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& w, const uint32_t* work_d, const uint32_t* count_d,
@@ -92,10 +75,11 @@ int launch_hamt_list_long(ipcfp_ctx* ctx, const void* meta_d, uint32_t n, uint32
     return IPCFP_OK;
 }
 
-int launch_hamt_node_table_lane(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta_d, uint32_t n, uint32_t kinds, void* recs_d) {
+int launch_hamt_node_table_lane(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta_d, uint32_t n, uint32_t below_len, uint32_t kinds,
+                                void* recs_d) {
     if (n == 0) return IPCFP_OK;
     hipLaunchKernelGGL(k_hamt_node_table_lane, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, arena, static_cast<const K1Meta*>(meta_d), n,
-                       kinds, static_cast<HamtNodeRec*>(recs_d));
+                       below_len, kinds, static_cast<HamtNodeRec*>(recs_d));
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }

@@ -54,8 +54,7 @@ int launch_hamt_get_levels(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& r
                            void* etabs_d = nullptr /* etab_cap × HamtEntryTab (hamt_table.h): the visited nodes' bucket entries */,
                            uint32_t etab_cap = 0);
 
-// --- hamt_table.hip / walk.hip --- the HAMT node table of a witness (hamt_table.h) and K7 over it
-int launch_hamt_node_table(ipcfp_ctx* ctx, const uint8_t* arena, const void* k1_meta_d, uint32_t n_blocks, uint32_t kinds, void* recs_d);
+// --- walk.hip --- K7 over the HAMT node table of a witness (hamt_table.h; the table's kernels: hamt_table_lane.hip below)
 uint32_t hamt_kind_bit(int vkind);  // HK_* bit of a value kind, 0: the table does not know that kind
 int launch_hamt_get_table(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const CidKey& root, uint32_t bit_width,
                           int vkind, const uint8_t* keys_d, const uint32_t* key_off_d, const uint32_t* key_len_d, uint32_t n,
@@ -236,11 +235,13 @@ int launch_subset_tables(ipcfp_ctx* ctx, const uint32_t* ids_d, uint32_t n, uint
                          uint8_t* cids_d, uint32_t* bad_d);
 
 int launch_claims_window(ipcfp_ctx* ctx, const void* claims_d, uint32_t n, unsigned long long* win_d);         // claims_compact.hip
-// --- the per-call HAMT node table in two kernels (hamt_table_lane.hip, hamt_levels.hip) ---
+// --- the per-call HAMT node table (hamt_table_lane.hip, hamt_levels.hip): one lane per block shorter than `below_len`
+// (the storage call: kHamtOutlineMinLen, the 32-lane outline and _rest take the longer ones; ipcfp_hamt_get*'s table: ~0) ---
 int launch_hamt_list_long(ipcfp_ctx* ctx, const void* meta_d, uint32_t n, uint32_t* work_d, uint32_t* count_d);
 int launch_hamt_outline_list(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& w, void* recs_d, uint32_t* work_d, uint32_t* count_d,
                              uint32_t bound);
-int launch_hamt_node_table_lane(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta_d, uint32_t n, uint32_t kinds, void* recs_d);
+int launch_hamt_node_table_lane(ipcfp_ctx* ctx, const uint8_t* arena, const void* meta_d, uint32_t n, uint32_t below_len, uint32_t kinds,
+                                void* recs_d);
 int launch_hamt_node_table_rest(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& w, const uint32_t* work_d, const uint32_t* count_d,
                                 uint32_t bound, uint32_t kinds, void* recs_d);
 int launch_rebase_claims(ipcfp_ctx* ctx, void* claims_d, uint32_t n, uint64_t base, uint64_t blob_len, uint64_t full_len,

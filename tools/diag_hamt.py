@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostics of the group-of-8 HAMT kernels on the GPU box: how many queries each kernel settles, per-kernel times
-(run under `rocprofv3 --kernel-trace --stats`)."""
+"""Diagnostics of the HAMT routes on configs[3]'s state tree: the statuses `hamt_get` and the storage call settle and their
+wall times (run under `rocprofv3 --kernel-trace --stats` for the per-kernel times)."""
 import os
 import sys
 import time
