@@ -13,6 +13,8 @@
 //!     `verify_storage_proof`          src/proofs/storage/verifier.rs:24-63
 //!     `verify_proof_bundle[_json]`    src/proofs/verifier.rs:12-62
 //!     `generate_proof_bundle`         src/proofs/generator.rs:25-95
+//!     `generate_event_proofs`         src/proofs/events/generator.rs:75-178 with the EventProofs of :262-297 lowered on
+//!                                     the device (`ipcfp_generate_event_claims`) and spelled by the library
 //!     `impl Blockstore for Witness`   src/proofs/common/blockstore.rs:26-39 (get / put_keyed / has)
 //!   A string with an interior NUL cannot cross a C ABI; the reference would fail to parse it (CID fields) or find it
 //!   unequal (compared fields), so the wrappers replace NUL by 0x01 — a byte that is in no multibase / hex alphabet
@@ -39,6 +41,8 @@ use crate::proofs::trust::TrustPolicy;
 #[repr(C)] pub struct ipcfp_witness_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_bundle_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_packed_events_t { _p: [u8; 0] }
+#[repr(C)] pub struct ipcfp_unpacked_events_t { _p: [u8; 0] }
+#[repr(C)] pub struct ipcfp_generated_events_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_storage_columns_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_comm_t { _p: [u8; 0] }
 
@@ -558,6 +562,44 @@ impl Witness<'_> {
             blocks.push(ProofBlock { cid, data });
         }
         Ok(UnifiedProofBundle { storage_proofs, event_proofs, blocks })
+    }
+
+    /// `generate_event_proof` for one filter (src/proofs/events/generator.rs:75-178): the `EventProof`s of
+    /// `find_matching_events` (:262-297) and the ids of the recorded blocks in `Cid: Ord` order.  The device lowers the
+    /// matches to packed claims (`ipcfp_generate_event_claims`) and the library spells them (`ipcfp_generated_events_proofs`:
+    /// "0x" + lowercase hex, `Cid::to_string()`), so no event is read back and decoded here.  The strings are copied: the
+    /// proofs are owned.  Err: the status the reference's `?` surfaces first, or a proof that names a CID longer than the
+    /// 40-byte slot (the claim keeps only its fold — include/ipcfp.h "CIDs").
+    pub fn generate_event_proofs(&self, parent_cids: &[Cid], child_cid: &Cid, filter: &ipcfp_event_filter_t,
+                                 actor_id_filter: Option<u64>) -> Result<(Vec<EventProof>, Vec<u32>)> {
+        let mut pc = Vec::new();
+        for c in parent_cids { pc.extend_from_slice(&cid_slot(c)?); }
+        let child = cid_slot(child_cid)?;
+        let (mut st, mut g) = (0u8, std::ptr::null_mut::<ipcfp_generated_events_t>());
+        let rc = unsafe { ipcfp_generate_event_claims(self.eng.ctx, self.raw(), pc.as_ptr(), parent_cids.len() as u32, child.as_ptr(), filter,
+                                                      actor_id_filter.is_some() as c_int, actor_id_filter.unwrap_or(0), &mut st, &mut g) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_generate_event_claims", rc)); }
+        if st != IPCFP_ST_TRUE || g.is_null() { return Err(anyhow!("generate_event_proof failed with status {st}")); }
+        struct Guard(*mut ipcfp_generated_events_t);
+        impl Drop for Guard { fn drop(&mut self) { unsafe { ipcfp_generated_events_destroy(self.0) } } }
+        let _guard = Guard(g);
+        let (mut proofs, mut n, mut bad) = (std::ptr::null::<ipcfp_event_proof_t>(), 0u64, u64::MAX);
+        let rc = unsafe { ipcfp_generated_events_proofs(g, &mut proofs, &mut n, &mut bad) };
+        if rc != 0 { return Err(anyhow!("{} (proof {bad})", self.eng.err("ipcfp_generated_events_proofs", rc))); }
+        let s = |p: *const c_char| unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned();
+        let list = |p: *const *const c_char, n: u32| (0..n as usize).map(|k| s(unsafe { *p.add(k) })).collect::<Vec<String>>();
+        let mut out = Vec::with_capacity(n as usize);
+        for k in 0..n as usize {
+            let p = unsafe { &*proofs.add(k) };
+            out.push(EventProof {
+                parent_epoch: p.parent_epoch, child_epoch: p.child_epoch, parent_tipset_cids: list(p.parent_tipset_cids, p.n_parent_tipset_cids),
+                child_block_cid: s(p.child_block_cid), message_cid: s(p.message_cid), exec_index: p.exec_index, event_index: p.event_index,
+                event_data: EventData { emitter: p.emitter, topics: list(p.topics, p.n_topics), data: s(p.data) } });
+        }
+        let mut nb = 0u64;
+        let ids = unsafe { ipcfp_generated_events_block_ids(g, &mut nb) };
+        let block_ids = if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() };
+        Ok((out, block_ids))
     }
 }
 

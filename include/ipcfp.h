@@ -182,7 +182,10 @@ enum {
     IPCFP_K_ALLGATHER = 13, /* ipcfp_allgather_segments: message packing + ncclAllGather */
     IPCFP_K_TIPSET_PROLOGUE = 14, /* header decodes, TxMeta re-hash, AMT roots (events/verifier.rs:147-181, utils.rs:48-72) */
     IPCFP_K_AMT_WALK = 15,        /* the dense Amt::for_each of message lists + receipts (levels and leaves) */
-    IPCFP_K_COUNT = 16
+    IPCFP_K_CLAIM_SIZES = 16,     /* ipcfp_event_claims_from_matches_device: decode + segment sizes, one lane per match */
+    IPCFP_K_CLAIM_SCAN = 17,      /* … the prefix sum over the segment sizes */
+    IPCFP_K_CLAIM_FILL = 18,      /* … claim records, flag-and-topic bytes, data */
+    IPCFP_K_COUNT = 19
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -679,6 +682,82 @@ void ipcfp_packed_events_destroy(ipcfp_packed_events_t* p);
 const ipcfp_tipset_ref_t* ipcfp_packed_events_tipsets(const ipcfp_packed_events_t* p, uint32_t* n);
 const ipcfp_event_claim_t* ipcfp_packed_events_claims(const ipcfp_packed_events_t* p, uint64_t* n);
 const uint8_t* ipcfp_packed_events_blob(const ipcfp_packed_events_t* p, uint64_t* len);
+
+/* The inverse, host only (no context, no device; parallel over claim ranges): packed claims → the reference's structs,
+ * with the strings the reference writes — "0x" + lowercase hex for topics and data, `Cid::to_string()` for every CID.
+ * Proofs of one tipset share that tipset's string arrays.  The handle owns every string.  All or nothing: *bad_index
+ * (nullable) receives the lowest offending claim, UINT64_MAX when there is none.
+ *   IPCFP_E_INVALID      a claim no EventProof lowers to: a topic whose flag byte is 0, a claim without both
+ *                        IPCFP_CLAIM_* bits, topics or data outside the blob, `tipset` >= n_tipsets, a tipset without
+ *                        both parsed flags (or wider than the inline form without more_parents), a slot that is not one
+ *                        well-formed CID
+ *   IPCFP_E_UNSUPPORTED  a folded CID slot (message, parent or child): its bytes are not in the claim                 */
+typedef struct ipcfp_unpacked_events ipcfp_unpacked_events_t;
+int ipcfp_unpack_event_claims(const ipcfp_tipset_ref_t* tipsets, uint32_t n_tipsets, const ipcfp_event_claim_t* claims,
+                              uint64_t n, const uint8_t* blob, uint64_t blob_len, ipcfp_unpacked_events_t** out,
+                              uint64_t* bad_index);
+const ipcfp_event_proof_t* ipcfp_unpacked_events_proofs(const ipcfp_unpacked_events_t* u, uint64_t* n);
+void ipcfp_unpacked_events_destroy(ipcfp_unpacked_events_t* u);
+
+/* ---- generated matches → packed claims, on the device ------------------------------------------------------------
+ * The last step of `find_matching_events` (src/proofs/events/generator.rs:262-297): each match becomes an `EventProof`
+ * whose `event_data.topics` / `.data` are `extract_evm_log(&se.event)` (src/proofs/common/evm.rs:13-59) of the located
+ * StampedEvent.  Here the proofs are written in the PACKED form (ipcfp_event_claim_t[n] + blob, below), byte for byte
+ * what ipcfp_pack_event_proofs makes of those EventProofs: the blob tight and in claim order — per claim
+ * n_topics x [01, topic[32]], then the data bytes; topics_off = the claim's segment start, data_off = that + 33 n_topics
+ * (also when data_len == 0: "0x" is matchable); flags = IPCFP_CLAIM_MSG_PARSED | IPCFP_CLAIM_DATA_MATCHABLE;
+ * message_cid = slot i of message_cids40_d as given (a folded slot stays folded); emitter, exec_index, event_index from
+ * the match; the two epochs and the tipset index as given.
+ *   matches_d          device, ipcfp_event_match_t[n] (ipcfp_scan_events_device, or any records that name items of w)
+ *   message_cids40_d   device, n slots in claim order
+ *   claims_out_d       device, room for n ipcfp_event_claim_t (8-byte aligned)
+ *   blob_out_d / cap_blob / *blob_len_out   the buffer contract of ipcfp_bundle_write_json: *blob_len_out always receives
+ *                      the exact length; blob_out_d == NULL with cap_blob == 0 is the sizing call (nothing is written,
+ *                      claims_out_d may be NULL); cap_blob < *blob_len_out is IPCFP_E_INVALID and nothing is written; a
+ *                      blob of 3.75 GB or more is IPCFP_E_UNSUPPORTED; n == 0 is IPCFP_OK with *blob_len_out = 0
+ * A record that cannot be lowered — its location is outside the witness (or block == 0xffffffff), the bytes at
+ * [off, off+len) are not exactly one well-formed StampedEvent, or extract_evm_log of it is None — becomes a claim with
+ * tipset = 0xffffffff, flags = 0, n_topics = topics_off = data_off = data_len = 0 (the other fields as given) and no blob
+ * bytes: IPCFP_ST_ERR_BAD_CLAIM when verified, the convention of ipcfp_expand_event_claims_device.  Synchronous.     */
+int ipcfp_event_claims_from_matches_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const void* matches_d, uint64_t n,
+                                           const void* message_cids40_d, int64_t parent_epoch, int64_t child_epoch,
+                                           uint32_t tipset, void* claims_out_d, void* blob_out_d, uint64_t cap_blob,
+                                           uint64_t* blob_len_out);
+
+/* ipcfp_generate_event_proofs whose proofs stay in HBM as packed claims (parent_epoch = the height of parent 0,
+ * child_epoch = the child's height, tipset = 0): the same steps, then ipcfp_event_claims_from_matches_device.
+ *   *status_out   exactly ipcfp_generate_event_proofs' status; anything but IPCFP_ST_TRUE: *out = NULL, IPCFP_OK
+ *   *out          owns its device memory (the context's pool: destroy it BEFORE the context) and what it hands out
+ * Accessors (pointers are the handle's, valid until it is destroyed):
+ *   _count          number of proofs
+ *   _tipset         the one ipcfp_tipset_ref_t the claims index (host; both parsed flags set; a key wider than the inline
+ *                   form behind more_parents, owned by the handle)
+ *   _claims_device / _blob_device   HBM: ipcfp_event_claim_t[count], the blob (*blob_len bytes) — what
+ *                   ipcfp_verify_event_claims_device takes
+ *   _copy           claims and blob to host buffers (claims_out: count records; blob_out: cap_blob >= the blob length,
+ *                   else IPCFP_E_INVALID; either may be NULL)
+ *   _matches / _message_cids   host copies of the match records and the message CID slots (made on first use; NULL when
+ *                   that copy fails: ipcfp_last_error)
+ *   _block_ids      the materialised witness: block ids of w in `Cid: Ord` order
+ *   _proofs         the EventProofs as the reference spells them (ipcfp_unpack_event_claims of the host copy; built on
+ *                   first use, strings owned by the handle); IPCFP_E_UNSUPPORTED with *bad_index = the first proof that
+ *                   has a folded CID (a CID longer than the slot, whose bytes only the witness block holds)          */
+typedef struct ipcfp_generated_events ipcfp_generated_events_t;
+int ipcfp_generate_event_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* parent_cids40, uint32_t n_parents,
+                                const uint8_t* child_cid40, const ipcfp_event_filter_t* filter, int has_actor,
+                                uint64_t actor, ipcfp_status_t* status_out, ipcfp_generated_events_t** out);
+void ipcfp_generated_events_destroy(ipcfp_generated_events_t* g);
+uint64_t ipcfp_generated_events_count(const ipcfp_generated_events_t* g);
+const ipcfp_tipset_ref_t* ipcfp_generated_events_tipset(const ipcfp_generated_events_t* g);
+const void* ipcfp_generated_events_claims_device(const ipcfp_generated_events_t* g);
+const void* ipcfp_generated_events_blob_device(const ipcfp_generated_events_t* g, uint64_t* blob_len);
+int ipcfp_generated_events_copy(ipcfp_generated_events_t* g, ipcfp_event_claim_t* claims_out, uint8_t* blob_out,
+                                uint64_t cap_blob);
+const ipcfp_event_match_t* ipcfp_generated_events_matches(ipcfp_generated_events_t* g, uint64_t* n);
+const uint8_t* ipcfp_generated_events_message_cids(ipcfp_generated_events_t* g, uint64_t* n);
+const uint32_t* ipcfp_generated_events_block_ids(const ipcfp_generated_events_t* g, uint64_t* n);
+int ipcfp_generated_events_proofs(ipcfp_generated_events_t* g, const ipcfp_event_proof_t** proofs, uint64_t* n,
+                                  uint64_t* bad_index);
 
 #define IPCFP_SCLAIM_CHILD_PARSED 1u        /* child_block_cid parses (storage/verifier.rs:85)              */
 #define IPCFP_SCLAIM_STATE_ROOT_CANON 2u    /* parent_state_root parses and equals its Cid::to_string()     */

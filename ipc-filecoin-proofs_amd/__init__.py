@@ -40,4 +40,7 @@ from .binding import (  # noqa: F401
     MATCH_DTYPE,
     witness_cut_host,
     route_event_claims,
+    GeneratedEvents,
+    UnpackedEvents,
+    unpack_event_claims,
 )

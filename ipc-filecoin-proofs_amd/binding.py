@@ -54,6 +54,10 @@ __all__ = [
     "compact_storage_claims",
     "expand_storage_claims",
     "StorageColumns",
+    "GeneratedEvents",
+    "unpack_event_claims",
+    "UnpackedEvents",
+    "EventProofStruct",
     "cid_from_string",
     "cid_to_string",
     "pack_cids",
@@ -88,6 +92,9 @@ KERNEL_IDS = {
     "allgather": 13,
     "tipset_prologue": 14,
     "amt_walk": 15,
+    "claim_sizes": 16,
+    "claim_scan": 17,
+    "claim_fill": 18,
 }
 
 
@@ -366,6 +373,21 @@ def load_library() -> C.CDLL:
         "ipcfp_bundle_event_proofs": (vp, [vp]),
         "ipcfp_bundle_storage_proofs": (vp, [vp]),
         "ipcfp_verify_proof_bundle": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ipcfp_event_claims_from_matches_device": (i32, [vp, vp, vp, u64, vp, C.c_int64, C.c_int64, C.c_uint32, vp, vp, u64, C.POINTER(u64)]),
+        "ipcfp_generate_event_claims": (i32, [vp, vp, vp, C.c_uint32, vp, vp, i32, u64, vp, C.POINTER(vp)]),
+        "ipcfp_generated_events_destroy": (None, [vp]),
+        "ipcfp_generated_events_count": (u64, [vp]),
+        "ipcfp_generated_events_tipset": (vp, [vp]),
+        "ipcfp_generated_events_claims_device": (vp, [vp]),
+        "ipcfp_generated_events_blob_device": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_events_copy": (i32, [vp, vp, vp, u64]),
+        "ipcfp_generated_events_matches": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_events_message_cids": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_events_block_ids": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_events_proofs": (i32, [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
+        "ipcfp_unpack_event_claims": (i32, [vp, C.c_uint32, vp, u64, vp, u64, C.POINTER(vp), C.POINTER(u64)]),
+        "ipcfp_unpacked_events_proofs": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_unpacked_events_destroy": (None, [vp]),
         "ipcfp_bundle_write_claims_json": (i32, [vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
         "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
     }
@@ -950,6 +972,155 @@ def expand_storage_claims(cols: StorageColumns) -> np.ndarray:
     return out
 
 
+class EventProofStruct(C.Structure):
+    """ipcfp_event_proof_t (include/ipcfp.h): the view UnpackedEvents / GeneratedEvents.proofs() hand out."""
+
+    _fields_ = [("parent_epoch", C.c_int64), ("child_epoch", C.c_int64), ("parent_tipset_cids", C.POINTER(C.c_char_p)),
+                ("n_parent_tipset_cids", C.c_uint32), ("child_block_cid", C.c_char_p), ("message_cid", C.c_char_p),
+                ("exec_index", C.c_uint64), ("event_index", C.c_uint64), ("emitter", C.c_uint64),
+                ("topics", C.POINTER(C.c_char_p)), ("n_topics", C.c_uint32), ("data", C.c_char_p)]
+
+
+def _proof_rows(ptr: int, n: int):
+    """ipcfp_event_proof_t[n] at an address → a list of dicts holding Python copies of every field (no pointer survives)."""
+    arr = (EventProofStruct * n).from_address(ptr) if n else []
+    rows = []
+    for p in arr:
+        rows.append({"parent_epoch": p.parent_epoch, "child_epoch": p.child_epoch,
+                     "parent_tipset_cids": [p.parent_tipset_cids[k].decode() for k in range(p.n_parent_tipset_cids)],
+                     "child_block_cid": p.child_block_cid.decode(), "message_cid": p.message_cid.decode(),
+                     "exec_index": p.exec_index, "event_index": p.event_index, "emitter": p.emitter,
+                     "topics": [p.topics[k].decode() for k in range(p.n_topics)], "data": p.data.decode()})
+    return rows
+
+
+class UnpackedEvents:
+    """EventProof structs with the reference's strings (ipcfp_unpacked_events_t): owns the handle; `ptr` / `n` are the
+    ipcfp_event_proof_t array (valid until close()) for the entry points that take claim structs."""
+
+    def __init__(self, handle):
+        self.lib = load_library()
+        self.h = handle
+        n = C.c_uint64()
+        self.ptr = self.lib.ipcfp_unpacked_events_proofs(handle, C.byref(n)) or 0
+        self.n = int(n.value)
+
+    def rows(self):
+        return _proof_rows(self.ptr, self.n)
+
+    def close(self):
+        if self.h:
+            self.lib.ipcfp_unpacked_events_destroy(self.h)
+            self.h = None
+            self.ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def unpack_event_claims(tipsets: np.ndarray, claims: np.ndarray, blob: np.ndarray, blob_len=None) -> UnpackedEvents:
+    """Host-only inverse of pack_event_proofs (ipcfp_unpack_event_claims; no GPU): packed claims → EventProof structs.
+    A refusal raises EngineError with `.rc` (the IPCFP_E_* code) and `.bad_index` (the lowest offending claim)."""
+    lib = load_library()
+    ts = np.ascontiguousarray(tipsets, dtype=TIPSET_DTYPE)
+    cl = np.ascontiguousarray(claims, dtype=CLAIM_DTYPE)
+    bl = np.ascontiguousarray(blob, dtype=np.uint8)
+    h, bad = C.c_void_p(), C.c_uint64()
+    rc = lib.ipcfp_unpack_event_claims(_p(ts) if len(ts) else None, len(ts), _p(cl) if len(cl) else None, len(cl),
+                                       _p(bl) if len(bl) else None, len(bl) if blob_len is None else int(blob_len), C.byref(h),
+                                       C.byref(bad))
+    if rc != 0:
+        e = EngineError(f"unpack_event_claims: claim {bad.value}: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+        e.rc, e.bad_index = rc, int(bad.value)
+        raise e
+    return UnpackedEvents(h)
+
+
+class GeneratedEvents:
+    """The proofs of one generate_event_proof call as packed claims resident in HBM (ipcfp_generated_events_t): owns the
+    handle — close it before the engine.  `claims_ptr` / `blob_ptr` / `blob_len` / `tipsets` are what
+    Witness.verify_event_claims_device takes."""
+
+    def __init__(self, eng: "Engine", handle):
+        self.eng = eng
+        self.lib = eng.lib
+        self.h = handle
+        lib = self.lib
+        self.n = int(lib.ipcfp_generated_events_count(handle))
+        bl = C.c_uint64()
+        self.claims_ptr = lib.ipcfp_generated_events_claims_device(handle) or 0
+        self.blob_ptr = lib.ipcfp_generated_events_blob_device(handle, C.byref(bl)) or 0
+        self.blob_len = int(bl.value)
+        buf = (C.c_uint8 * TIPSET_DTYPE.itemsize).from_address(lib.ipcfp_generated_events_tipset(handle))
+        self.tipsets = np.frombuffer(buf, dtype=TIPSET_DTYPE)  # one record; more_parents points into the handle
+        nb = C.c_uint64()
+        pb = lib.ipcfp_generated_events_block_ids(handle, C.byref(nb))
+        self.block_ids = (np.frombuffer((C.c_uint8 * (4 * nb.value)).from_address(pb), dtype=np.uint32).copy() if nb.value
+                          else np.zeros(0, np.uint32))
+
+    def copy(self):
+        """→ (claims CLAIM_DTYPE[n], blob u8[blob_len]) on the host."""
+        claims = np.zeros(self.n, dtype=CLAIM_DTYPE)
+        blob = np.zeros(self.blob_len, dtype=np.uint8)
+        self.eng._check(self.lib.ipcfp_generated_events_copy(self.h, _p(claims) if self.n else None,
+                                                             _p(blob) if self.blob_len else None, self.blob_len),
+                        "generated_events_copy")
+        return claims, blob
+
+    def matches(self):
+        """→ (match records MATCH_DTYPE[n], message CID slots u8[n, 40]) on the host."""
+        n = C.c_uint64()
+        pm = self.lib.ipcfp_generated_events_matches(self.h, C.byref(n))
+        pc = self.lib.ipcfp_generated_events_message_cids(self.h, C.byref(n))
+        if pm is None and pc is None and self.n:
+            self.eng._check(-3, "generated_events_matches")
+        if not self.n:
+            return np.zeros(0, dtype=MATCH_DTYPE), np.zeros((0, CID_SLOT), dtype=np.uint8)
+        m = np.frombuffer((C.c_uint8 * (MATCH_DTYPE.itemsize * self.n)).from_address(pm), dtype=MATCH_DTYPE).copy()
+        c = np.frombuffer((C.c_uint8 * (CID_SLOT * self.n)).from_address(pc), dtype=np.uint8).reshape(-1, CID_SLOT).copy()
+        return m, c
+
+    def proofs(self):
+        """→ (address of ipcfp_event_proof_t[n], n): the reference's strings, owned by the handle (valid until close()).
+        EngineError with `.rc` / `.bad_index` when a proof has no string form (a folded CID: IPCFP_E_UNSUPPORTED)."""
+        p, n, bad = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.ipcfp_generated_events_proofs(self.h, C.byref(p), C.byref(n), C.byref(bad))
+        if rc != 0:
+            msg = self.lib.ipcfp_last_error(self.eng.h)
+            e = EngineError(f"generated_events_proofs: {msg.decode() if msg else ''} ({rc})")
+            e.rc, e.bad_index = rc, int(bad.value)
+            raise e
+        return (p.value or 0), int(n.value)
+
+    def proof_rows(self):
+        return _proof_rows(*self.proofs())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.tipsets = None
+            if self.eng.h:  # a context that is already gone took its device memory with it
+                self.lib.ipcfp_generated_events_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def bundle_check_json(text: bytes, flags: int = 0):
     """Host half of the bundle parse (no GPU): → (ok, n_storage, n_events, n_blocks, error text)."""
     lib = load_library()
@@ -1250,6 +1421,29 @@ class Witness:
             self.eng._check(self.lib.ipcfp_generate_event_proofs(*args, _p(m), _p(msg), len(m), C.byref(npf), _p(ids),
                                                                  None, len(ids), C.byref(nb)), "generate_event_proofs")
         return int(st[0]), m, msg, ids
+
+    def generate_event_claims(self, parent_cids, child_cid: bytes, topic0: bytes, topic1: bytes, actor=None):
+        """generate_event_proof whose proofs stay in HBM as packed claims (ipcfp_generate_event_claims).
+        → (status, GeneratedEvents or None when the status is not 1)."""
+        pc = pack_cids(parent_cids)
+        child = cid_slots([child_cid])[0].copy()
+        filt = np.frombuffer(bytes(topic0) + bytes(topic1), dtype=np.uint8).copy()
+        st = np.zeros(1, dtype=np.uint8)
+        h = C.c_void_p()
+        a = (0, 0) if actor is None else (1, int(actor))
+        self.eng._check(self.lib.ipcfp_generate_event_claims(self.eng.h, self.h, _p(pc), len(parent_cids), _p(child), _p(filt),
+                                                             a[0], a[1], _p(st), C.byref(h)), "generate_event_claims")
+        return int(st[0]), (GeneratedEvents(self.eng, h) if h.value else None)
+
+    def event_claims_from_matches_device(self, matches_ptr: int, n: int, message_cids_ptr: int, parent_epoch: int, child_epoch: int,
+                                         tipset: int, claims_out_ptr: int, blob_out_ptr: int, cap_blob: int):
+        """ipcfp_event_claims_from_matches_device over device pointers → (rc, blob length).  The return code is handed
+        back (not raised): IPCFP_E_INVALID for a short buffer and IPCFP_E_UNSUPPORTED are results a caller branches on."""
+        bl = C.c_uint64()
+        rc = self.lib.ipcfp_event_claims_from_matches_device(self.eng.h, self.h, matches_ptr or None, n, message_cids_ptr or None,
+                                                             parent_epoch, child_epoch, tipset, claims_out_ptr or None,
+                                                             blob_out_ptr or None, cap_blob, C.byref(bl))
+        return int(rc), int(bl.value)
 
     def generate_storage_proofs(self, child_cid: bytes, actor_ids, slots32):
         """generate_storage_proof for n (actor_id, slot) specs.  Returns (records GEN_STORAGE_DTYPE[n],

@@ -12,6 +12,8 @@
 // src/proofs/common/witness.rs:34-54 iterates a BTreeSet<Cid>).
 #include <algorithm>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "../common.h"
@@ -124,6 +126,179 @@ static_assert(sizeof(StorageGenHost) == sizeof(ipcfp_generated_storage_t), "gene
 
 }  // namespace
 
+namespace {
+
+// What `generate_event_proof` leaves behind on the DEVICE, before anything is copied out: both generator entry points
+// run this and differ only in what they do with it.
+struct EventGenCore {
+    uint32_t status = IPCFP_ST_ERR;
+    TipsetCtxDev tc;      // the host copy after the header kernel: heights, receipts root
+    WideParents wide;
+    DevBuf<uint32_t> touched;  // the recorder's bitmap (+ 2 flag words)
+    ScanResult scan;      // scan.matches: the match records
+    DevBuf<CidKey> msg;   // message CID of match i
+    uint64_t nm = 0;
+};
+
+// Steps 1-6 of generate_event_proof and the base witness marks.  IPCFP_OK with core.status != IPCFP_ST_TRUE: the Err the
+// reference's `?` surfaces first (nothing else of `core` is then meaningful).
+int generate_events_core(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent_cids40, uint32_t n_parents, const uint8_t* child_cid40,
+                         const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor, EventGenCore& core) {
+    core.status = IPCFP_ST_ERR;
+    const uint32_t words = div_up(uint32_t(w->n), 32);
+    DevBuf<uint32_t>& touched = core.touched;
+    IPCFP_HIP(ctx, touched.alloc(words + 2));
+    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words + 2) * 4, ctx->stream));
+    uint32_t* oor_d = touched.p + words;          // an exec_index is outside the execution order
+    uint32_t* missing_d = touched.p + words + 1;  // a base CID is absent from the store
+    const WitnessView rec = witness_view(w, touched.p);
+
+    // Step 1 (generator.rs:89-95): child header → receipts root.  The context kernel also loads parent 0.
+    TipsetCtxDev& tc = core.tc;
+    WideParents& wide = core.wide;
+    if (int rc_t = tipset_inputs_list(ctx, TC_PARENTS_PARSED | TC_CHILD_PARSED, parent_cids40, n_parents, child_cid40, tc, wide)) return rc_t;
+    DevBuf<TipsetCtxDev> tc_d;
+    IPCFP_HIP(ctx, tc_d.alloc(1));
+    IPCFP_HIP(ctx, hipMemcpyAsync(tc_d.p, &tc, sizeof tc, hipMemcpyHostToDevice, ctx->stream));
+    int rc = launch_ctx_headers(ctx, rec, tc_d.p, 1);
+    if (rc) return rc;
+    IPCFP_HIP(ctx, d2h_small(ctx, &tc, tc_d.p, sizeof tc, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    if (tc.child_status != IPCFP_ST_TRUE) {
+        core.status = tc.child_status;
+        return IPCFP_OK;
+    }
+    // Steps 2-4 (generator.rs:97-135): parent headers, TxMeta, the message AMTs (recorded) and the
+    // execution order with verify_txmeta = false.  One traversal serves record_transaction_amts and
+    // build_execution_order: both load exactly the same blocks in the same order.
+    ExecState ex;
+    rc = build_exec_order(ctx, rec, tc_d.p, n_parents, ex, /*verify_txmeta=*/0);
+    if (rc) return rc;
+    if (ex.status != IPCFP_ST_TRUE) {
+        core.status = ex.status;
+        return IPCFP_OK;
+    }
+    // Step 5 (generator.rs:137-150): two-pass scan, recording
+    ScanResult& scan = core.scan;
+    rc = scan_events_device(ctx, w, tc.receipts_root, *filter, has_actor, actor, touched.p, scan);
+    if (rc) return rc;
+    if (scan.status != IPCFP_ST_TRUE) {
+        core.status = scan.status;
+        return IPCFP_OK;
+    }
+    // Step 6 (generator.rs:152-169): message CID of each match = exec_list[exec_index]; the records stay where they are
+    const uint64_t nm = scan.n_matches;
+    if (nm >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "too many matches");
+    DevBuf<CidKey> exec_list;
+    DevBuf<uint64_t> exec_idx;
+    if (nm) {
+        IPCFP_HIP(ctx, exec_list.alloc(ex.exec_len ? ex.exec_len : 1));
+        IPCFP_HIP(ctx, core.msg.alloc(nm));
+        rc = launch_exec_compact(ctx, ex.keys.p, uint32_t(ex.raw_len), ex.first.p, ex.pos.p, exec_list.p);
+        if (rc) return rc;
+        IPCFP_HIP(ctx, exec_idx.alloc(nm));
+        rc = launch_match_exec_index(ctx, scan.matches.p, uint32_t(nm), exec_idx.p);
+        if (rc) return rc;
+        rc = launch_gather_keys(ctx, exec_list.p, ex.exec_len, exec_idx.p, uint32_t(nm), core.msg.p, oor_d);
+        if (rc) return rc;
+    }
+    // base witness (generator.rs:97-112): parents, child, receipts root (TxMeta CIDs were marked by the traversal)
+    std::vector<CidKey> base;
+    tipset_parent_keys(tc, wide, base);
+    base.push_back(tc.child);
+    base.push_back(tc.receipts_root);
+    DevBuf<CidKey> base_d;
+    IPCFP_HIP(ctx, base_d.alloc(base.size()));
+    IPCFP_HIP(ctx, hipMemcpyAsync(base_d.p, base.data(), base.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_mark_cids(ctx, rec, base_d.p, uint32_t(base.size()), missing_d);
+    if (rc) return rc;
+    uint32_t flag[2] = {0, 0};
+    IPCFP_HIP(ctx, d2h_small(ctx, flag, oor_d, 8, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));  // (also: exec_list, exec_idx and base_d are no longer read)
+    if (flag[0]) {  // "Missing message at index" (generator.rs:158-160) precedes materialisation
+        core.status = IPCFP_ST_ERR;
+        return IPCFP_OK;
+    }
+    if (flag[1]) {  // must_get of a base CID fails (witness.rs:45-48)
+        core.status = IPCFP_ST_ERR_MISSING_BLOCK;
+        return IPCFP_OK;
+    }
+    core.nm = nm;
+    core.status = IPCFP_ST_TRUE;
+    return IPCFP_OK;
+}
+
+// ipcfp_event_claims_from_matches_device behind its argument checks.  `plan_only`: stop behind the sizes.
+struct ClaimGenPlan {
+    DevBuf<uint8_t> recs;  // GenRec[n]
+    DevBuf<uint64_t> sizes, prefix, scratch, total_d;
+    uint64_t total = 0;
+};
+
+int claim_gen_plan(ipcfp_ctx* ctx, ipcfp_witness* w, const void* matches_d, uint32_t n, ClaimGenPlan& plan) {
+    plan.total = 0;
+    if (n == 0) return IPCFP_OK;
+    IPCFP_HIP(ctx, plan.recs.alloc(size_t(n) * 32));
+    IPCFP_HIP(ctx, plan.sizes.alloc(n));
+    IPCFP_HIP(ctx, plan.prefix.alloc(n));
+    IPCFP_HIP(ctx, plan.scratch.alloc(size_t(div_up(n, 1024)) + 1));
+    IPCFP_HIP(ctx, plan.total_d.alloc(1));
+    const int rc = launch_gen_claim_sizes(ctx, witness_view(w), matches_d, n, plan.recs.p, plan.sizes.p, plan.prefix.p, plan.total_d.p,
+                                          plan.scratch.p);
+    if (rc) return rc;
+    IPCFP_HIP(ctx, d2h_small(ctx, &plan.total, plan.total_d.p, 8, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    if (plan.total >= 0xf0000000ULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "event_claims_from_matches: a claim blob of %llu bytes (limit 3.75 GB)",
+                                                     (unsigned long long)plan.total);
+    return IPCFP_OK;
+}
+
+}  // namespace
+
+// The handle of ipcfp_generate_event_claims: claims and blob in HBM, everything else on the host.
+struct ipcfp_generated_events {
+    ipcfp_ctx* ctx = nullptr;
+    uint64_t n = 0, blob_len = 0;
+    DevBuf<ipcfp::EventClaimPacked> claims_d;
+    DevBuf<uint8_t> blob_d;
+    DevBuf<ipcfp_event_match_t> matches_d;
+    DevBuf<CidKey> msg_d;
+    ipcfp_tipset_ref_t tipset;
+    std::vector<uint8_t> more_parents;
+    std::vector<uint32_t> block_ids;
+    // host copies, made on first use
+    bool have_host = false;
+    std::vector<ipcfp_event_claim_t> claims_h;
+    std::vector<uint8_t> blob_h;
+    std::vector<ipcfp_event_match_t> matches_h;
+    std::vector<uint8_t> msg_h;
+    ipcfp_unpacked_events_t* unpacked = nullptr;
+};
+
+namespace {
+
+int generated_host_copy(ipcfp_generated_events* g) {
+    if (g->have_host) return IPCFP_OK;
+    ipcfp_ctx* ctx = g->ctx;
+    IPCFP_ENTER(ctx);
+    g->claims_h.resize(g->n);
+    g->blob_h.resize(g->blob_len);
+    g->matches_h.resize(g->n);
+    g->msg_h.resize(g->n * IPCFP_CID_SLOT);
+    if (g->n) {
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->claims_h.data(), g->claims_d.p, g->n * sizeof(ipcfp_event_claim_t), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->matches_h.data(), g->matches_d.p, g->n * sizeof(ipcfp_event_match_t), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->msg_h.data(), g->msg_d.p, g->n * IPCFP_CID_SLOT, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (g->blob_len)
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->blob_h.data(), g->blob_d.p, g->blob_len, hipMemcpyDeviceToHost, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    g->have_host = true;
+    return IPCFP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int ipcfp_generate_event_proofs(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* parent_cids40, uint32_t n_parents,
@@ -138,99 +313,171 @@ int ipcfp_generate_event_proofs(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint
     IPCFP_ENTER(ctx);
     *n_proofs = *n_blocks = 0;
     *status_out = IPCFP_ST_ERR;
-
-    const uint32_t words = div_up(uint32_t(w->n), 32);
-    DevBuf<uint32_t> touched;
-    IPCFP_HIP(ctx, touched.alloc(words + 2));
-    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words + 2) * 4, ctx->stream));
-    uint32_t* oor_d = touched.p + words;          // an exec_index is outside the execution order
-    uint32_t* missing_d = touched.p + words + 1;  // a base CID is absent from the store
-    const WitnessView rec = witness_view(w, touched.p);
-
-    // Step 1 (generator.rs:89-95): child header → receipts root.  The context kernel also loads parent 0.
-    TipsetCtxDev tc;
-    WideParents wide;
-    if (int rc_t = tipset_inputs_list(ctx, TC_PARENTS_PARSED | TC_CHILD_PARSED, parent_cids40, n_parents, child_cid40, tc, wide)) return rc_t;
-    DevBuf<TipsetCtxDev> tc_d;
-    IPCFP_HIP(ctx, tc_d.alloc(1));
-    IPCFP_HIP(ctx, hipMemcpyAsync(tc_d.p, &tc, sizeof tc, hipMemcpyHostToDevice, ctx->stream));
-    int rc = launch_ctx_headers(ctx, rec, tc_d.p, 1);
+    EventGenCore core;
+    int rc = generate_events_core(ctx, w, parent_cids40, n_parents, child_cid40, filter, has_actor, actor, core);
     if (rc) return rc;
-    IPCFP_HIP(ctx, d2h_small(ctx, &tc, tc_d.p, sizeof tc, ctx->stream));
-    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
-    if (tc.child_status != IPCFP_ST_TRUE) {
-        *status_out = ipcfp_status_t(tc.child_status);
+    if (core.status != IPCFP_ST_TRUE) {
+        *status_out = ipcfp_status_t(core.status);
         return IPCFP_OK;
     }
-    // Steps 2-4 (generator.rs:97-135): parent headers, TxMeta, the message AMTs (recorded) and the
-    // execution order with verify_txmeta = false.  One traversal serves record_transaction_amts and
-    // build_execution_order: both load exactly the same blocks in the same order.
-    ExecState ex;
-    rc = build_exec_order(ctx, rec, tc_d.p, n_parents, ex, /*verify_txmeta=*/0);
-    if (rc) return rc;
-    if (ex.status != IPCFP_ST_TRUE) {
-        *status_out = ipcfp_status_t(ex.status);
-        return IPCFP_OK;
-    }
-    // Step 5 (generator.rs:137-150): two-pass scan, recording
-    ScanResult scan;
-    rc = scan_events_device(ctx, w, tc.receipts_root, *filter, has_actor, actor, touched.p, scan);
-    if (rc) return rc;
-    if (scan.status != IPCFP_ST_TRUE) {
-        *status_out = ipcfp_status_t(scan.status);
-        return IPCFP_OK;
-    }
-    // Step 6 (generator.rs:152-169): message CID of each match = exec_list[exec_index]
-    const uint64_t nm = scan.n_matches;
-    if (nm >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "too many matches");
-    DevBuf<CidKey> exec_list, msg;
-    DevBuf<uint64_t> exec_idx;
-    if (nm) {
-        IPCFP_HIP(ctx, exec_list.alloc(ex.exec_len ? ex.exec_len : 1));
-        IPCFP_HIP(ctx, msg.alloc(nm));
-        rc = launch_exec_compact(ctx, ex.keys.p, uint32_t(ex.raw_len), ex.first.p, ex.pos.p, exec_list.p);
-        if (rc) return rc;
-        std::vector<ipcfp_event_match_t> mh(nm);
-        IPCFP_HIP(ctx, hipMemcpyAsync(mh.data(), scan.matches.p, nm * sizeof(ipcfp_event_match_t), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-        IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
-        std::vector<uint64_t> idx(nm);
-        for (uint64_t i = 0; i < nm; ++i) idx[i] = mh[i].exec_index;
-        IPCFP_HIP(ctx, exec_idx.alloc(nm));
-        IPCFP_HIP(ctx, hipMemcpyAsync(exec_idx.p, idx.data(), nm * 8, hipMemcpyHostToDevice, ctx->stream));
-        rc = launch_gather_keys(ctx, exec_list.p, ex.exec_len, exec_idx.p, uint32_t(nm), msg.p, oor_d);
-        if (rc) return rc;
-        const uint64_t take = nm < cap_proofs ? nm : cap_proofs;
-        if (matches) std::memcpy(matches, mh.data(), take * sizeof(ipcfp_event_match_t));
-        if (message_cids40)
-            IPCFP_HIP(ctx, hipMemcpyAsync(message_cids40, msg.p, take * IPCFP_CID_SLOT, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    // base witness (generator.rs:97-112): parents, child, receipts root (TxMeta CIDs were marked by the traversal)
-    std::vector<CidKey> base;
-    tipset_parent_keys(tc, wide, base);
-    base.push_back(tc.child);
-    base.push_back(tc.receipts_root);
-    DevBuf<CidKey> base_d;
-    IPCFP_HIP(ctx, base_d.alloc(base.size()));
-    IPCFP_HIP(ctx, hipMemcpyAsync(base_d.p, base.data(), base.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_mark_cids(ctx, rec, base_d.p, uint32_t(base.size()), missing_d);
-    if (rc) return rc;
-    uint32_t flag[2] = {0, 0};
-    IPCFP_HIP(ctx, d2h_small(ctx, flag, oor_d, 8, ctx->stream));
-    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
-    if (flag[0]) {  // "Missing message at index" (generator.rs:158-160) precedes materialisation
-        *status_out = IPCFP_ST_ERR;
-        return IPCFP_OK;
-    }
-    if (flag[1]) {  // must_get of a base CID fails (witness.rs:45-48)
-        *status_out = IPCFP_ST_ERR_MISSING_BLOCK;
-        return IPCFP_OK;
-    }
+    const uint64_t take = core.nm < cap_proofs ? core.nm : cap_proofs;
+    if (take && matches)
+        IPCFP_HIP(ctx, hipMemcpyAsync(matches, core.scan.matches.p, take * sizeof(ipcfp_event_match_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (take && message_cids40)
+        IPCFP_HIP(ctx, hipMemcpyAsync(message_cids40, core.msg.p, take * IPCFP_CID_SLOT, hipMemcpyDeviceToHost, ctx->stream));
     // Step 7 (generator.rs:171-177): materialise in BTreeSet order
-    rc = materialize(ctx, w, touched.p, witness_block_ids, witness_cids40, cap_blocks, n_blocks);
+    rc = materialize(ctx, w, core.touched.p, witness_block_ids, witness_cids40, cap_blocks, n_blocks);
     if (rc) return rc;
-    *n_proofs = nm;
+    *n_proofs = core.nm;
     *status_out = IPCFP_ST_TRUE;
+    return IPCFP_OK;
+}
+
+int ipcfp_event_claims_from_matches_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const void* matches_d, uint64_t n,
+                                           const void* message_cids40_d, int64_t parent_epoch, int64_t child_epoch,
+                                           uint32_t tipset, void* claims_out_d, void* blob_out_d, uint64_t cap_blob,
+                                           uint64_t* blob_len_out) {
+    if (!ctx || !w || w->ctx != ctx || !blob_len_out) return IPCFP_E_INVALID;
+    *blob_len_out = 0;
+    IPCFP_ENTER(ctx);
+    if (!blob_out_d && cap_blob) return set_error(ctx, IPCFP_E_INVALID, "event_claims_from_matches: no blob buffer but a capacity");
+    if (n == 0) return IPCFP_OK;
+    if (n >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "event_claims_from_matches: batch too large");
+    const bool sizing = !blob_out_d;
+    if (!matches_d || (!sizing && (!message_cids40_d || !claims_out_d)))
+        return set_error(ctx, IPCFP_E_INVALID, "event_claims_from_matches: null matches, message CIDs or claim buffer");
+    ClaimGenPlan plan;
+    int rc = claim_gen_plan(ctx, w, matches_d, uint32_t(n), plan);
+    *blob_len_out = plan.total;
+    if (rc) return rc;
+    if (sizing) return IPCFP_OK;
+    if (cap_blob < plan.total)
+        return set_error(ctx, IPCFP_E_INVALID, "event_claims_from_matches: the blob is %llu bytes, the buffer holds %llu",
+                         (unsigned long long)plan.total, (unsigned long long)cap_blob);
+    rc = launch_gen_claim_fill(ctx, witness_view(w), matches_d, static_cast<const CidKey*>(message_cids40_d), uint32_t(n), plan.recs.p,
+                               plan.prefix.p, plan.total, parent_epoch, child_epoch, tipset, claims_out_d, static_cast<uint8_t*>(blob_out_d));
+    if (rc) return rc;
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream, true));
+    return IPCFP_OK;
+}
+
+int ipcfp_generate_event_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* parent_cids40, uint32_t n_parents,
+                                const uint8_t* child_cid40, const ipcfp_event_filter_t* filter, int has_actor,
+                                uint64_t actor, ipcfp_status_t* status_out, ipcfp_generated_events_t** out) {
+    if (!ctx || !w || w->ctx != ctx || !child_cid40 || !filter || !status_out || !out || (n_parents && !parent_cids40))
+        return IPCFP_E_INVALID;
+    *out = nullptr;
+    IPCFP_ENTER(ctx);
+    *status_out = IPCFP_ST_ERR;
+    EventGenCore core;
+    int rc = generate_events_core(ctx, w, parent_cids40, n_parents, child_cid40, filter, has_actor, actor, core);
+    if (rc) return rc;
+    if (core.status != IPCFP_ST_TRUE) {
+        *status_out = ipcfp_status_t(core.status);
+        return IPCFP_OK;
+    }
+    std::unique_ptr<ipcfp_generated_events, void (*)(ipcfp_generated_events*)> g(new (std::nothrow) ipcfp_generated_events(),
+                                                                                ipcfp_generated_events_destroy);
+    if (!g) return set_error(ctx, IPCFP_E_NOMEM, "generate_event_claims: out of memory");
+    g->ctx = ctx;
+    g->n = core.nm;
+    // the one tipset the claims name: the key as it was given (a folded slot stays folded)
+    std::memset(&g->tipset, 0, sizeof g->tipset);
+    g->tipset.flags = TC_PARENTS_PARSED | TC_CHILD_PARSED;
+    g->tipset.n_parents = n_parents;
+    std::memcpy(g->tipset.child, child_cid40, IPCFP_CID_SLOT);
+    const uint32_t n_inline = n_parents < uint32_t(IPCFP_MAX_PARENTS) ? n_parents : uint32_t(IPCFP_MAX_PARENTS);
+    if (n_inline) std::memcpy(g->tipset.parents, parent_cids40, size_t(n_inline) * IPCFP_CID_SLOT);
+    if (n_parents > n_inline) {
+        g->more_parents.assign(parent_cids40 + size_t(n_inline) * IPCFP_CID_SLOT, parent_cids40 + size_t(n_parents) * IPCFP_CID_SLOT);
+        g->tipset.more_parents = g->more_parents.data();
+    }
+    // the lowering: sizes, prefix, then a blob of exactly that length
+    ClaimGenPlan plan;
+    rc = claim_gen_plan(ctx, w, core.scan.matches.p, uint32_t(core.nm), plan);
+    if (rc) return rc;
+    g->blob_len = plan.total;
+    if (core.nm) {
+        IPCFP_HIP(ctx, g->claims_d.alloc(core.nm));
+        IPCFP_HIP(ctx, g->blob_d.alloc(plan.total + 16));
+        rc = launch_gen_claim_fill(ctx, witness_view(w), core.scan.matches.p, core.msg.p, uint32_t(core.nm), plan.recs.p, plan.prefix.p,
+                                   plan.total, core.tc.parent0_height, core.tc.child_height, 0u, g->claims_d.p, g->blob_d.p);
+        if (rc) {
+            (void)sync_stream(ctx, ctx->stream);
+            return rc;
+        }
+    }
+    // Step 7 (generator.rs:171-177): materialise in BTreeSet order (synchronises: the fill is done when it returns)
+    uint64_t nb = 0;
+    g->block_ids.resize(w->n ? w->n : 1);
+    rc = materialize(ctx, w, core.touched.p, g->block_ids.data(), nullptr, g->block_ids.size(), &nb);
+    if (rc) {
+        (void)sync_stream(ctx, ctx->stream);
+        return rc;
+    }
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream, true));
+    g->block_ids.resize(nb);
+    g->matches_d.swap(core.scan.matches);
+    g->msg_d.swap(core.msg);
+    *status_out = IPCFP_ST_TRUE;
+    *out = g.release();
+    return IPCFP_OK;
+}
+
+void ipcfp_generated_events_destroy(ipcfp_generated_events_t* g) {
+    if (!g) return;
+    if (g->unpacked) ipcfp_unpacked_events_destroy(g->unpacked);
+    delete g;
+}
+uint64_t ipcfp_generated_events_count(const ipcfp_generated_events_t* g) { return g ? g->n : 0; }
+const ipcfp_tipset_ref_t* ipcfp_generated_events_tipset(const ipcfp_generated_events_t* g) { return g ? &g->tipset : nullptr; }
+const void* ipcfp_generated_events_claims_device(const ipcfp_generated_events_t* g) { return g ? g->claims_d.p : nullptr; }
+const void* ipcfp_generated_events_blob_device(const ipcfp_generated_events_t* g, uint64_t* blob_len) {
+    if (blob_len) *blob_len = g ? g->blob_len : 0;
+    return g ? g->blob_d.p : nullptr;
+}
+int ipcfp_generated_events_copy(ipcfp_generated_events_t* g, ipcfp_event_claim_t* claims_out, uint8_t* blob_out, uint64_t cap_blob) {
+    if (!g) return IPCFP_E_INVALID;
+    if (blob_out && cap_blob < g->blob_len)
+        return set_error(g->ctx, IPCFP_E_INVALID, "generated_events_copy: the blob is %llu bytes, the buffer holds %llu",
+                         (unsigned long long)g->blob_len, (unsigned long long)cap_blob);
+    if (const int rc = generated_host_copy(g)) return rc;
+    if (claims_out && g->n) std::memcpy(claims_out, g->claims_h.data(), g->n * sizeof(ipcfp_event_claim_t));
+    if (blob_out && g->blob_len) std::memcpy(blob_out, g->blob_h.data(), g->blob_len);
+    return IPCFP_OK;
+}
+const ipcfp_event_match_t* ipcfp_generated_events_matches(ipcfp_generated_events_t* g, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || generated_host_copy(g)) return nullptr;
+    if (n) *n = g->n;
+    return g->matches_h.data();
+}
+const uint8_t* ipcfp_generated_events_message_cids(ipcfp_generated_events_t* g, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || generated_host_copy(g)) return nullptr;
+    if (n) *n = g->n;
+    return g->msg_h.data();
+}
+const uint32_t* ipcfp_generated_events_block_ids(const ipcfp_generated_events_t* g, uint64_t* n) {
+    if (n) *n = g ? g->block_ids.size() : 0;
+    return g ? g->block_ids.data() : nullptr;
+}
+int ipcfp_generated_events_proofs(ipcfp_generated_events_t* g, const ipcfp_event_proof_t** proofs, uint64_t* n, uint64_t* bad_index) {
+    if (!g || !proofs || !n) return IPCFP_E_INVALID;
+    *proofs = nullptr;
+    *n = 0;
+    if (bad_index) *bad_index = ~0ull;
+    if (!g->unpacked) {
+        if (const int rc = generated_host_copy(g)) return rc;
+        uint64_t bad = ~0ull;
+        const int rc = ipcfp_unpack_event_claims(&g->tipset, 1, g->claims_h.data(), g->n, g->blob_h.data(), g->blob_len, &g->unpacked, &bad);
+        if (bad_index) *bad_index = bad;
+        if (rc == IPCFP_E_UNSUPPORTED)
+            return set_error(g->ctx, rc, "generated_events_proofs: a CID of proof %llu is longer than the %d-byte slot and the claim keeps only its fold",
+                             (unsigned long long)bad, int(IPCFP_CID_SLOT));
+        if (rc) return set_error(g->ctx, rc, "generated_events_proofs: claim %llu does not unpack", (unsigned long long)bad);
+    }
+    *proofs = ipcfp_unpacked_events_proofs(g->unpacked, n);
     return IPCFP_OK;
 }
 

@@ -108,6 +108,20 @@ int launch_gather_keys(ipcfp_ctx* ctx, const CidKey* table_d, uint64_t table_len
     return IPCFP_OK;
 }
 
+// the exec_index column of the match records, for launch_gather_keys (the records stay in HBM)
+__global__ __launch_bounds__(256) void k_match_exec_index(const ipcfp_event_match_t* __restrict__ m, uint32_t n, uint64_t* __restrict__ idx) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) idx[i] = m[i].exec_index;
+}
+
+int launch_match_exec_index(ipcfp_ctx* ctx, const void* matches_d, uint32_t n, uint64_t* idx_d) {
+    if (n == 0) return IPCFP_OK;
+    hipLaunchKernelGGL(k_match_exec_index, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
+                       static_cast<const ipcfp_event_match_t*>(matches_d), n, idx_d);
+    IPCFP_HIP(ctx, hipGetLastError());
+    return IPCFP_OK;
+}
+
 int launch_gather_block_cids(ipcfp_ctx* ctx, const uint8_t* cids_d, const uint32_t* ids_d, uint32_t n, CidKey* out_d) {
     if (n == 0) return IPCFP_OK;
     hipLaunchKernelGGL(k_gather_block_cids, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, cids_d, ids_d, n, out_d);

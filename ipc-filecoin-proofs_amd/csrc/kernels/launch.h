@@ -109,6 +109,19 @@ int launch_expand_claims(ipcfp_ctx* ctx, const void* compact_d, uint32_t n, cons
                          const uint8_t* cblob_d, uint64_t cblob_len, void* claims_out_d, uint8_t* blob_out_d, uint64_t cap_blob,
                          uint32_t* scratch_u32, uint64_t* scan_scratch);
 
+// --- event_claims_gen.hip --- generated matches → EventClaimPacked[n] + blob (ipcfp_event_claims_from_matches_device)
+// one lane per match: bounds check, decode_event_log over exactly the item, the claim's blob segment size and its GenRec
+// (32 B: where the topics and the data lie, so that the fill decodes nothing); then size_d's prefix sum into off_d / *total_d
+// scratch_d: div_up(n, 1024) + 1 u64
+int launch_gen_claim_sizes(ipcfp_ctx* ctx, const WitnessView& w, const void* matches_d, uint32_t n, void* recs_d, uint64_t* size_d,
+                           uint64_t* off_d, uint64_t* total_d, uint64_t* scratch_d);
+// the claim records and the blob's `total` bytes (total < 2^32; blob_out_d holds at least that many)
+int launch_gen_claim_fill(ipcfp_ctx* ctx, const WitnessView& w, const void* matches_d, const CidKey* message_d, uint32_t n,
+                          const void* recs_d, const uint64_t* off_d, uint64_t total, long long parent_epoch, long long child_epoch,
+                          uint32_t tipset, void* claims_out_d, uint8_t* blob_out_d);
+// idx_d[i] = matches_d[i].exec_index (generate.hip)
+int launch_match_exec_index(ipcfp_ctx* ctx, const void* matches_d, uint32_t n, uint64_t* idx_d);
+
 // --- scan.hip ---
 int launch_scan_u32(ipcfp_ctx* ctx, const uint32_t* in_d, uint32_t n, uint32_t* out_d, uint64_t* total_d,
                     uint64_t* scratch_d);
