@@ -133,3 +133,67 @@ STORAGE_CASES = {
     "b1_bit_width_0": lambda **o: _storage_case(_b1_saying(0), _sc().S[0], _sc().VAL[0], ERR_DECODE, **o),
     "b1_bit_width_9": lambda **o: _storage_case(_b1_saying(9), _sc().S[0], _sc().VAL[0], ERR_DECODE, **o),
 }
+
+
+# --- fvm_ipld_amt and fvm_shared as the EVENT chain meets them (tests/event_chain_cases.py `tipset`) ----------------------------
+# Each case: name → callable → (store, claim fields, expected status of verify_event_proof).  tests/pyevents.py names each
+# assumption with a constant and makes the choice the oracle and the engine were written to make; a case here pins what the
+# three do, it does not prove the crate does it.  tests/test_event_chain.py holds pyevents and the oracle to the table,
+# tests/test_gpu_event_chain.py every route of the engine.
+def _ec():
+    import event_chain_cases as ec
+
+    return ec
+
+
+def _event_case(make_root, fields: dict, expect: int, salt: int):
+    """receipt 2 of the default tipset gets the events root `make_root(store)`; the claim names it with `fields`"""
+    ec = _ec()
+    store, claim, _ = ec.tipset(salt=salt, receipts={**ec.default_receipts(6), 2: lambda st: pyamt.receipt(events_root=make_root(st))})
+    claim.update(fields)
+    return store, claim, expect
+
+
+def _ev(emitter=900):
+    return _ec().good_event(emitter)
+
+
+def _claim_for(j, emitter=900, **over):
+    return {"event_index": j, **_ec().log_fields(_ev(emitter)), **over}
+
+
+def _root(bw=5, height=0, count=1, bitmap=b"\x01\x00\x00\x00", values=None, links=()):
+    ec = _ec()
+    return lambda st: ec.raw_root(st, [_ev()] if values is None else values, bitmap, bw=bw, height=height, count=uint(count), links=links)
+
+
+def _entry_event(flags, codec):
+    ec = _ec()
+    return ec.stamped(900, [ec.entry("t1", ec.T[0], flags=flags, codec=codec), ec.entry("t2", ec.T[1], flags=flags, codec=codec)])
+
+
+EVENT_CASES = {
+    # AMT_COUNT_IS_NOT_CHECKED
+    "events_root_count_0_over_one_value": lambda: _event_case(_root(count=0), _claim_for(0), TRUE, 1),
+    "events_root_count_2_pow_40_over_one_value": lambda: _event_case(_root(count=1 << 40), _claim_for(0), TRUE, 2),
+    # AMT_MAX_HEIGHT_IS_64_OVER_BIT_WIDTH: at bit width 8 a height of 8 loads, 9 is an Err of the load
+    "events_root_height_8_at_bit_width_8_loads": lambda: _event_case(_root(bw=8, height=8, count=0, bitmap=bytes(32), values=[]), _claim_for(0), 11, 3),
+    "events_root_height_9_at_bit_width_8": lambda: _event_case(_root(bw=8, height=9, count=0, bitmap=bytes(32), values=[]), _claim_for(0), ERR_DECODE, 4),
+    "events_root_height_13_at_bit_width_5": lambda: _event_case(_root(height=13, count=0, bitmap=bytes(4), values=[]), _claim_for(0), ERR_DECODE, 5),
+    # AMT_MAX_INDEX_IS_U64_MAX_MINUS_1: the generic Err (64) for u64::MAX, None for the index below it
+    "event_index_u64_max": lambda: _event_case(_root(), _claim_for((1 << 64) - 1), 64, 6),
+    "event_index_u64_max_minus_1": lambda: _event_case(_root(), _claim_for((1 << 64) - 2), 11, 7),
+    # AMT_LINKS_AT_HEIGHT_0_ARE_AN_ERR_OF_THE_WALK
+    "events_root_height_0_with_a_link_index_0": lambda: _event_case(_root(values=[], links=[pyamt.cid_of(b"nowhere")]), _claim_for(0), ERR_DECODE, 8),
+    "events_root_height_0_with_a_link_index_32": lambda: _event_case(_root(values=[], links=[pyamt.cid_of(b"nowhere")]), _claim_for(32), 11, 9),
+    # AMT_BIT_WIDTH_IS_1_TO_8
+    "events_root_bit_width_0": lambda: _event_case(_root(bw=0, bitmap=b"\x01"), _claim_for(0), ERR_DECODE, 10),
+    "events_root_bit_width_9": lambda: _event_case(_root(bw=9, bitmap=b"\x01" + bytes(63)), _claim_for(0), ERR_DECODE, 11),
+    # ENTRY_FLAGS_AND_CODEC_ARE_ANY_U64
+    "entry_flags_and_codec_u64_max": lambda: _event_case(_root(values=[_entry_event((1 << 64) - 1, (1 << 64) - 1)]),
+                                                          {"event_index": 0, **_ec().log_fields(_entry_event(0, 0))}, TRUE, 12),
+    # serde_ipld_dagcbor accepts a non-minimal integer (nonminimal_uint_argument_is_accepted above), also where the event
+    # table's fast decodes expect the short spelling: the emitter and a key's length
+    "emitter_900_spelled_in_four_bytes": lambda: _event_case(_root(values=[b"\x82\x1a\x00\x00\x03\x84" + _ev()[4:]]), _claim_for(0), TRUE, 13),
+    "emitter_5_spelled_in_two_bytes": lambda: _event_case(_root(values=[b"\x82\x19\x00\x05" + _ev()[4:]]), {**_claim_for(0), "emitter": 5}, TRUE, 14),
+}
