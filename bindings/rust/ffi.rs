@@ -43,6 +43,8 @@ use crate::proofs::trust::TrustPolicy;
 #[repr(C)] pub struct ipcfp_packed_events_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_unpacked_events_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_generated_events_t { _p: [u8; 0] }
+#[repr(C)] pub struct ipcfp_generated_storage_claims_t { _p: [u8; 0] }
+#[repr(C)] pub struct ipcfp_unpacked_storage_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_storage_columns_t { _p: [u8; 0] }
 #[repr(C)] pub struct ipcfp_comm_t { _p: [u8; 0] }
 
@@ -601,6 +603,132 @@ impl Witness<'_> {
         let block_ids = if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() };
         Ok((out, block_ids))
     }
+
+    /// `generate_storage_proof` for a batch of specs of one child block (src/proofs/storage/generator.rs:29-178), in the
+    /// order `generate_proof_bundle` walks them: the device leaves the proofs as column claims in HBM
+    /// (`ipcfp_generate_storage_claims`) and the library spells them (`ipcfp_generated_storage_claims_proofs`).  Returns the
+    /// owned `StorageProof`s and the ids of the recorded blocks in `Cid: Ord` order.  Err: the first failing spec (where
+    /// `generate_proof_bundle` aborts), or a proof that names a CID longer than the 40-byte slot.
+    pub fn generate_storage_claims(&self, child_cid: &Cid, child_epoch: i64, specs: &[(u64, [u8; 32])]) -> Result<(Vec<StorageProof>, Vec<u32>)> {
+        let child = cid_slot(child_cid)?;
+        let actors: Vec<u64> = specs.iter().map(|s| s.0).collect();
+        let mut slots = Vec::with_capacity(specs.len() * 32);
+        for s in specs { slots.extend_from_slice(&s.1); }
+        let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
+        let rc = unsafe { ipcfp_generate_storage_claims(self.eng.ctx, self.raw(), child.as_ptr(), child_epoch, actors.as_ptr(), slots.as_ptr(),
+                                                        specs.len() as u64, &mut g) };
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims", rc)); }
+        struct Guard(*mut ipcfp_generated_storage_claims_t);
+        impl Drop for Guard { fn drop(&mut self) { unsafe { ipcfp_generated_storage_claims_destroy(self.0) } } }
+        let _guard = Guard(g);
+        let (mut proofs, mut n, mut bad) = (std::ptr::null::<ipcfp_storage_proof_t>(), 0u64, u64::MAX);
+        let rc = unsafe { ipcfp_generated_storage_claims_proofs(g, &mut proofs, &mut n, &mut bad) };
+        if rc != 0 { return Err(anyhow!("{} (spec {bad})", self.eng.err("ipcfp_generated_storage_claims_proofs", rc))); }
+        let s = |p: *const c_char| unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned();
+        let mut out = Vec::with_capacity(n as usize);
+        for k in 0..n as usize {
+            let p = unsafe { &*proofs.add(k) };
+            out.push(StorageProof {
+                child_epoch: p.child_epoch, child_block_cid: s(p.child_block_cid), parent_state_root: s(p.parent_state_root),
+                actor_id: p.actor_id, actor_state_cid: s(p.actor_state_cid), storage_root: s(p.storage_root), slot: s(p.slot),
+                value: s(p.value) });
+        }
+        let mut nb = 0u64;
+        let ids = unsafe { ipcfp_generated_storage_claims_block_ids(g, &mut nb) };
+        let block_ids = if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() };
+        Ok((out, block_ids))
+    }
+}
+
+/// The proofs of one `generate_storage_claims_handle` call as column claims resident in HBM (`ipcfp_generated_storage_claims_t`).
+/// The device pointers are the handle's and live as long as it does; it borrows the engine, so it is dropped before it.
+pub struct GeneratedStorageClaims<'e> { eng: &'e Engine, raw: *mut ipcfp_generated_storage_claims_t }
+
+impl Drop for GeneratedStorageClaims<'_> {
+    fn drop(&mut self) { unsafe { ipcfp_generated_storage_claims_destroy(self.raw) } }
+}
+
+impl GeneratedStorageClaims<'_> {
+    pub fn len(&self) -> u64 { unsafe { ipcfp_generated_storage_claims_count(self.raw) } }
+    pub fn is_empty(&self) -> bool { self.len() == 0 }
+    pub fn run_count(&self) -> u32 { unsafe { ipcfp_generated_storage_claims_run_count(self.raw) } }
+    /// (run table, slot column, value column, cflags column, status bytes) in HBM: what `verify_columns` passes on.
+    pub fn device_columns(&self) -> (*const std::ffi::c_void, *const std::ffi::c_void, *const std::ffi::c_void, *const std::ffi::c_void, *const std::ffi::c_void) {
+        unsafe { (ipcfp_generated_storage_claims_runs_device(self.raw), ipcfp_generated_storage_claims_slots_device(self.raw),
+                  ipcfp_generated_storage_claims_values_device(self.raw), ipcfp_generated_storage_claims_cflags_device(self.raw),
+                  ipcfp_generated_storage_claims_status_device(self.raw)) }
+    }
+    /// One status byte per spec (a host copy made on first use).
+    pub fn status(&mut self) -> Vec<u8> {
+        let mut n = 0u64;
+        let p = unsafe { ipcfp_generated_storage_claims_status(self.raw, &mut n) };
+        if p.is_null() || n == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(p, n as usize) }.to_vec() }
+    }
+    /// Index of the first spec whose status is not IPCFP_ST_TRUE: where `generate_proof_bundle` aborts (generator.rs:48-49).
+    pub fn first_error(&mut self) -> Option<u64> {
+        let v = unsafe { ipcfp_generated_storage_claims_first_error(self.raw) };
+        if v == u64::MAX { None } else { Some(v) }
+    }
+    /// Ids of the recorded blocks in `Cid: Ord` order.
+    pub fn block_ids(&self) -> Vec<u32> {
+        let mut nb = 0u64;
+        let ids = unsafe { ipcfp_generated_storage_claims_block_ids(self.raw, &mut nb) };
+        if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() }
+    }
+    /// `verify_storage_proof` of the handle's own columns against `w` (`ipcfp_verify_storage_columns_device`), status bytes
+    /// written to `status_d` (device memory, one byte per spec).
+    pub fn verify_columns(&self, w: &Witness<'_>, trust: Option<&ipcfp_trust_policy_t>, status_d: *mut std::ffi::c_void) -> Result<()> {
+        let (runs, slot, value, cflags, _) = self.device_columns();
+        let rc = unsafe { ipcfp_verify_storage_columns_device(self.eng.ctx, w.raw(), runs, self.run_count(), slot, value, cflags, self.len(),
+                                                              trust.map_or(std::ptr::null(), |t| t as *const _), status_d) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_verify_storage_columns_device", rc)); }
+        Ok(())
+    }
+}
+
+impl<'e> Witness<'e> {
+    /// `ipcfp_generate_storage_claims`: the specs from host memory, the proofs left in HBM behind a handle.
+    pub fn generate_storage_claims_handle(&self, child_cid: &Cid, child_epoch: i64, specs: &[(u64, [u8; 32])]) -> Result<GeneratedStorageClaims<'e>> {
+        let child = cid_slot(child_cid)?;
+        let actors: Vec<u64> = specs.iter().map(|s| s.0).collect();
+        let mut slots = Vec::with_capacity(specs.len() * 32);
+        for s in specs { slots.extend_from_slice(&s.1); }
+        let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
+        let rc = unsafe { ipcfp_generate_storage_claims(self.eng.ctx, self.raw(), child.as_ptr(), child_epoch, actors.as_ptr(), slots.as_ptr(),
+                                                        specs.len() as u64, &mut g) };
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims", rc)); }
+        Ok(GeneratedStorageClaims { eng: self.eng, raw: g })
+    }
+
+    /// `ipcfp_generate_storage_claims_device`: the specs resident in HBM.
+    ///
+    /// # Safety
+    /// `actor_ids_d` must point to `n` u64 and `slots32_d` (on a 16-byte boundary) to `32 n` bytes of device memory of this
+    /// engine's device, both valid for the duration of the call.
+    pub unsafe fn generate_storage_claims_device(&self, child_cid: &Cid, child_epoch: i64, actor_ids_d: *const std::ffi::c_void, slots32_d: *const std::ffi::c_void,
+                                                 n: u64) -> Result<GeneratedStorageClaims<'e>> {
+        let child = cid_slot(child_cid)?;
+        let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
+        let rc = ipcfp_generate_storage_claims_device(self.eng.ctx, self.raw(), child.as_ptr(), child_epoch, actor_ids_d, slots32_d, n, &mut g);
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims_device", rc)); }
+        Ok(GeneratedStorageClaims { eng: self.eng, raw: g })
+    }
+}
+
+/// `ipcfp_unpack_storage_claims` (host only): packed claims → owned `StorageProof`s in the reference's spelling.  Err names
+/// the lowest claim that no `StorageProof` lowers to, or whose CID slot is a fold.
+pub fn unpack_storage_claims(claims: &[ipcfp_storage_claim_t]) -> Result<Vec<StorageProof>> {
+    let (mut u, mut bad) = (std::ptr::null_mut::<ipcfp_unpacked_storage_t>(), u64::MAX);
+    let rc = unsafe { ipcfp_unpack_storage_claims(claims.as_ptr(), claims.len() as u64, &mut u, &mut bad) };
+    if rc != 0 { return Err(anyhow!("ipcfp_unpack_storage_claims: code {rc} at claim {bad}")); }
+    let mut n = 0u64;
+    let proofs = unsafe { ipcfp_unpacked_storage_proofs(u, &mut n) };
+    let s = |p: *const c_char| unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned();
+    let out = (0..n as usize).map(|k| { let p = unsafe { &*proofs.add(k) }; StorageProof {
+        child_epoch: p.child_epoch, child_block_cid: s(p.child_block_cid), parent_state_root: s(p.parent_state_root), actor_id: p.actor_id,
+        actor_state_cid: s(p.actor_state_cid), storage_root: s(p.storage_root), slot: s(p.slot), value: s(p.value) } }).collect();
+    unsafe { ipcfp_unpacked_storage_destroy(u) };
+    Ok(out)
 }
 
 /// The witness as the trait every fvm_ipld_amt / fvm_ipld_hamt call goes through

@@ -185,7 +185,10 @@ enum {
     IPCFP_K_CLAIM_SIZES = 16,     /* ipcfp_event_claims_from_matches_device: decode + segment sizes, one lane per match */
     IPCFP_K_CLAIM_SCAN = 17,      /* … the prefix sum over the segment sizes */
     IPCFP_K_CLAIM_FILL = 18,      /* … claim records, flag-and-topic bytes, data */
-    IPCFP_K_COUNT = 19
+    IPCFP_K_SGEN_RUNS = 19,       /* ipcfp_generate_storage_claims*: run discovery and the per-run chain (header … layout sniff) */
+    IPCFP_K_SGEN_SPECS = 20,      /* … the per-spec storage get: value, cflags, status (table kernel + one-lane kernel) */
+    IPCFP_K_SGEN_RECORDS = 21,    /* … the 192-byte run records */
+    IPCFP_K_COUNT = 22
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -854,6 +857,71 @@ int ipcfp_verify_storage_columns(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipc
  * ipcfp_expand_storage_claims gives.                                                                                */
 int ipcfp_expand_storage_claims_device(ipcfp_ctx_t* ctx, const void* runs_d, uint32_t n_runs, const void* slot_d,
                                        const void* value_d, const void* cflags_d, uint64_t n, void* claims_out_d);
+
+/* ---- the storage generator finished as column claims resident in HBM --------------------------------------------------
+ * `generate_storage_proof` + `create_proof_claim` (src/proofs/storage/generator.rs:29-178) for n (actor_id, slot) specs
+ * of ONE child block, in the order `generate_proof_bundle` walks them (src/proofs/generator.rs:42-56), left on the device
+ * in the column form above — what ipcfp_verify_storage_columns_device and ipcfp_expand_storage_claims_device take.
+ *   child_epoch   `child.height` of the caller's ApiTipset (generator.rs:169); not compared with the header's height
+ *   runs          the maximal stretches of consecutive specs with equal actor_id.  When every spec succeeds, run table
+ *                 and columns equal ipcfp_compact_storage_claims of the rows one would write by hand, byte for byte.
+ *   a spec with status IPCFP_ST_TRUE   its run record carries child_epoch, actor_id, child and the three derived CIDs
+ *                 (the header's parent_state_root, ActorState.state, EvmState.contract_state; a CID longer than the slot
+ *                 as its fold), flags = 15; slot as given, value = left_pad_32(read_storage_slot(..).unwrap_or_default()),
+ *                 cflags = 48
+ *   a failing spec   the status ipcfp_generate_storage_proofs gives; slot as given, value zero, cflags = 0.  Where the
+ *                 chain failed before contract_state was known (child header, StateRoot, actor get, EVM state) the whole
+ *                 run has flags = 0 and three zero CID slots; a later failure (storage root block missing, an Err inside
+ *                 the get) keeps flags = 15 and the CIDs.  Either way the claim is well formed and the column verifier
+ *                 answers IPCFP_ST_ERR_BAD_CLAIM for it.
+ *   n == 0: IPCFP_OK and an empty handle; n >= 2^32 - 1: IPCFP_E_UNSUPPORTED.
+ * The _device form takes the specs from HBM (actor_ids_d u64[n], slots32_d u8[n][32] on a 16-byte boundary).
+ * Route (tuning key "hamt_table", as ipcfp_verify_storage_proofs): over the per-call HAMT node table when 16 n >= the
+ * witness's block count, else one lane per spec; runs are shared on both.
+ * Accessors: every pointer is the handle's and stays valid until it is destroyed; destroy the handle before the context.
+ *   _runs_device / _slots_device / _values_device / _cflags_device   the column form, each on a 16-byte boundary
+ *   _status_device  one status byte per spec;  _status  a host copy made on first use
+ *   _first_error    index of the first spec whose status is not IPCFP_ST_TRUE, or UINT64_MAX — where
+ *                   `generate_proof_bundle` aborts (generator.rs:48-49)
+ *   _copy           runs and columns to caller buffers (any pointer may be NULL)
+ *   _block_ids      the materialised witness: ids of the recorded blocks in `Cid: Ord` order — id for id what
+ *                   ipcfp_generate_storage_proofs returns for the same arguments
+ *   _proofs         the StorageProofs as the reference spells them (ipcfp_unpack_storage_claims of the expanded host copy,
+ *                   built on first use); IPCFP_E_INVALID with *bad_index = first_error when a spec failed,
+ *                   IPCFP_E_UNSUPPORTED with the first proof that carries a folded CID                                  */
+typedef struct ipcfp_generated_storage_claims ipcfp_generated_storage_claims_t;
+int ipcfp_generate_storage_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cid40, int64_t child_epoch,
+                                  const uint64_t* actor_ids, const uint8_t* slots32, uint64_t n,
+                                  ipcfp_generated_storage_claims_t** out);
+int ipcfp_generate_storage_claims_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cid40, int64_t child_epoch,
+                                         const void* actor_ids_d, const void* slots32_d, uint64_t n,
+                                         ipcfp_generated_storage_claims_t** out);
+void ipcfp_generated_storage_claims_destroy(ipcfp_generated_storage_claims_t* g);
+uint64_t ipcfp_generated_storage_claims_count(const ipcfp_generated_storage_claims_t* g);
+uint32_t ipcfp_generated_storage_claims_run_count(const ipcfp_generated_storage_claims_t* g);
+const void* ipcfp_generated_storage_claims_runs_device(const ipcfp_generated_storage_claims_t* g);
+const void* ipcfp_generated_storage_claims_slots_device(const ipcfp_generated_storage_claims_t* g);
+const void* ipcfp_generated_storage_claims_values_device(const ipcfp_generated_storage_claims_t* g);
+const void* ipcfp_generated_storage_claims_cflags_device(const ipcfp_generated_storage_claims_t* g);
+const void* ipcfp_generated_storage_claims_status_device(const ipcfp_generated_storage_claims_t* g);
+const uint8_t* ipcfp_generated_storage_claims_status(ipcfp_generated_storage_claims_t* g, uint64_t* n);
+uint64_t ipcfp_generated_storage_claims_first_error(ipcfp_generated_storage_claims_t* g);
+int ipcfp_generated_storage_claims_copy(ipcfp_generated_storage_claims_t* g, uint8_t* runs_out, uint8_t* slots_out,
+                                        uint8_t* values_out, uint8_t* cflags_out);
+const uint32_t* ipcfp_generated_storage_claims_block_ids(const ipcfp_generated_storage_claims_t* g, uint64_t* n);
+int ipcfp_generated_storage_claims_proofs(ipcfp_generated_storage_claims_t* g, const ipcfp_storage_proof_t** proofs,
+                                          uint64_t* n, uint64_t* bad_index);
+
+/* The host inverse of ipcfp_pack_storage_proofs (no device, no context): packed claims → StorageProof structs with the
+ * strings the reference writes — every CID `Cid::to_string()`, slot and value `format!("0x{}", hex::encode(..))`
+ * (src/proofs/storage/generator.rs:158-178).  All or nothing; *bad_index (nullable) names the lowest offending claim.
+ * IPCFP_E_INVALID: a claim no StorageProof of this spelling lowers to (one of the six IPCFP_SCLAIM_* bits missing, unknown
+ * flag bits, reserved != 0, a CID slot that is not one well-formed CID); IPCFP_E_UNSUPPORTED: a folded CID slot.       */
+typedef struct ipcfp_unpacked_storage ipcfp_unpacked_storage_t;
+int ipcfp_unpack_storage_claims(const ipcfp_storage_claim_t* claims, uint64_t n, ipcfp_unpacked_storage_t** out,
+                                uint64_t* bad_index);
+const ipcfp_storage_proof_t* ipcfp_unpacked_storage_proofs(const ipcfp_unpacked_storage_t* u, uint64_t* n);
+void ipcfp_unpacked_storage_destroy(ipcfp_unpacked_storage_t* u);
 
 /* Rebuild the CID → block index of an existing witness in place (K4), e.g. once per verification
  * pass when the index build is to be charged to that pass.  No allocation.                    */

@@ -43,4 +43,8 @@ from .binding import (  # noqa: F401
     GeneratedEvents,
     UnpackedEvents,
     unpack_event_claims,
+    unpack_storage_claims,
+    GeneratedStorageClaims,
+    UnpackedStorage,
+    StorageProofStruct,
 )

@@ -57,6 +57,10 @@ __all__ = [
     "GeneratedEvents",
     "unpack_event_claims",
     "UnpackedEvents",
+    "GeneratedStorageClaims",
+    "unpack_storage_claims",
+    "UnpackedStorage",
+    "StorageProofStruct",
     "EventProofStruct",
     "cid_from_string",
     "cid_to_string",
@@ -95,6 +99,9 @@ KERNEL_IDS = {
     "claim_sizes": 16,
     "claim_scan": 17,
     "claim_fill": 18,
+    "sgen_runs": 19,
+    "sgen_specs": 20,
+    "sgen_records": 21,
 }
 
 
@@ -388,6 +395,24 @@ def load_library() -> C.CDLL:
         "ipcfp_unpack_event_claims": (i32, [vp, C.c_uint32, vp, u64, vp, u64, C.POINTER(vp), C.POINTER(u64)]),
         "ipcfp_unpacked_events_proofs": (vp, [vp, C.POINTER(u64)]),
         "ipcfp_unpacked_events_destroy": (None, [vp]),
+        "ipcfp_generate_storage_claims": (i32, [vp, vp, vp, C.c_int64, vp, vp, u64, C.POINTER(vp)]),
+        "ipcfp_generate_storage_claims_device": (i32, [vp, vp, vp, C.c_int64, vp, vp, u64, C.POINTER(vp)]),
+        "ipcfp_generated_storage_claims_destroy": (None, [vp]),
+        "ipcfp_generated_storage_claims_count": (u64, [vp]),
+        "ipcfp_generated_storage_claims_run_count": (C.c_uint32, [vp]),
+        "ipcfp_generated_storage_claims_runs_device": (vp, [vp]),
+        "ipcfp_generated_storage_claims_slots_device": (vp, [vp]),
+        "ipcfp_generated_storage_claims_values_device": (vp, [vp]),
+        "ipcfp_generated_storage_claims_cflags_device": (vp, [vp]),
+        "ipcfp_generated_storage_claims_status_device": (vp, [vp]),
+        "ipcfp_generated_storage_claims_status": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_storage_claims_first_error": (u64, [vp]),
+        "ipcfp_generated_storage_claims_copy": (i32, [vp, vp, vp, vp, vp]),
+        "ipcfp_generated_storage_claims_block_ids": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_generated_storage_claims_proofs": (i32, [vp, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]),
+        "ipcfp_unpack_storage_claims": (i32, [vp, u64, C.POINTER(vp), C.POINTER(u64)]),
+        "ipcfp_unpacked_storage_proofs": (vp, [vp, C.POINTER(u64)]),
+        "ipcfp_unpacked_storage_destroy": (None, [vp]),
         "ipcfp_bundle_write_claims_json": (i32, [vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
         "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
     }
@@ -1121,6 +1146,151 @@ class GeneratedEvents:
             pass
 
 
+class StorageProofStruct(C.Structure):
+    """ipcfp_storage_proof_t (include/ipcfp.h): the view UnpackedStorage / GeneratedStorageClaims.proofs() hand out."""
+
+    _fields_ = [("child_epoch", C.c_int64), ("child_block_cid", C.c_char_p), ("parent_state_root", C.c_char_p),
+                ("actor_id", C.c_uint64), ("actor_state_cid", C.c_char_p), ("storage_root", C.c_char_p), ("slot", C.c_char_p),
+                ("value", C.c_char_p)]
+
+
+def _storage_proof_rows(ptr: int, n: int):
+    """ipcfp_storage_proof_t[n] at an address → a list of dicts holding Python copies of every field."""
+    arr = (StorageProofStruct * n).from_address(ptr) if n else []
+    return [{"child_epoch": p.child_epoch, "child_block_cid": p.child_block_cid.decode(),
+             "parent_state_root": p.parent_state_root.decode(), "actor_id": p.actor_id,
+             "actor_state_cid": p.actor_state_cid.decode(), "storage_root": p.storage_root.decode(), "slot": p.slot.decode(),
+             "value": p.value.decode()} for p in arr]
+
+
+class UnpackedStorage:
+    """StorageProof structs with the reference's strings (ipcfp_unpacked_storage_t): owns the handle; `ptr` / `n` are the
+    ipcfp_storage_proof_t array (valid until close()) for the entry points that take claim structs."""
+
+    def __init__(self, handle):
+        self.lib = load_library()
+        self.h = handle
+        n = C.c_uint64()
+        self.ptr = self.lib.ipcfp_unpacked_storage_proofs(handle, C.byref(n)) or 0
+        self.n = int(n.value)
+
+    def rows(self):
+        return _storage_proof_rows(self.ptr, self.n)
+
+    def close(self):
+        if self.h:
+            self.lib.ipcfp_unpacked_storage_destroy(self.h)
+            self.h = None
+            self.ptr = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+def unpack_storage_claims(claims: np.ndarray) -> UnpackedStorage:
+    """Host-only inverse of pack_storage_proofs (ipcfp_unpack_storage_claims; no GPU): SCLAIM_DTYPE[n] → StorageProof structs.
+    A refusal raises EngineError with `.rc` (the IPCFP_E_* code) and `.bad_index` (the lowest offending claim)."""
+    lib = load_library()
+    cl = np.ascontiguousarray(claims, dtype=SCLAIM_DTYPE)
+    h, bad = C.c_void_p(), C.c_uint64()
+    rc = lib.ipcfp_unpack_storage_claims(_p(cl) if len(cl) else None, len(cl), C.byref(h), C.byref(bad))
+    if rc != 0:
+        e = EngineError(f"unpack_storage_claims: claim {bad.value}: {lib.ipcfp_strerror(rc).decode()} ({rc})")
+        e.rc, e.bad_index = rc, int(bad.value)
+        raise e
+    return UnpackedStorage(h)
+
+
+class GeneratedStorageClaims:
+    """The proofs of one batch of generate_storage_proof specs as column claims resident in HBM
+    (ipcfp_generated_storage_claims_t): owns the handle — close it before the engine.  `runs_ptr` / `n_runs` / `slot_ptr` /
+    `value_ptr` / `cflags_ptr` / `n` are what Witness.verify_storage_columns_device and expand_storage_claims_device take."""
+
+    def __init__(self, eng: "Engine", handle):
+        self.eng = eng
+        self.lib = eng.lib
+        self.h = handle
+        lib = self.lib
+        self.n = int(lib.ipcfp_generated_storage_claims_count(handle))
+        self.n_runs = int(lib.ipcfp_generated_storage_claims_run_count(handle))
+        self.runs_ptr = lib.ipcfp_generated_storage_claims_runs_device(handle) or 0
+        self.slot_ptr = lib.ipcfp_generated_storage_claims_slots_device(handle) or 0
+        self.value_ptr = lib.ipcfp_generated_storage_claims_values_device(handle) or 0
+        self.cflags_ptr = lib.ipcfp_generated_storage_claims_cflags_device(handle) or 0
+        self.status_ptr = lib.ipcfp_generated_storage_claims_status_device(handle) or 0
+        nb = C.c_uint64()
+        pb = lib.ipcfp_generated_storage_claims_block_ids(handle, C.byref(nb))
+        self.block_ids = (np.frombuffer((C.c_uint8 * (4 * nb.value)).from_address(pb), dtype=np.uint32).copy() if nb.value
+                          else np.zeros(0, np.uint32))
+
+    def status(self) -> np.ndarray:
+        """→ one status byte per spec (a host copy)."""
+        n = C.c_uint64()
+        ps = self.lib.ipcfp_generated_storage_claims_status(self.h, C.byref(n))
+        if not self.n:
+            return np.zeros(0, np.uint8)
+        if not ps:
+            self.eng._check(-3, "generated_storage_claims_status")
+        return np.frombuffer((C.c_uint8 * self.n).from_address(ps), dtype=np.uint8).copy()
+
+    @property
+    def first_error(self):
+        """Index of the first spec whose status is not 1, or None."""
+        v = int(self.lib.ipcfp_generated_storage_claims_first_error(self.h))
+        return None if v == 2**64 - 1 else v
+
+    def copy(self):
+        """→ (runs record[n_runs], slot u8[n, 32], value u8[n, 32], cflags u8[n]) on the host."""
+        runs = np.zeros(self.n_runs, dtype=_SRUN_DTYPE)
+        slot = np.zeros((self.n, 32), dtype=np.uint8)
+        value = np.zeros((self.n, 32), dtype=np.uint8)
+        cflags = np.zeros(self.n, dtype=np.uint8)
+        self.eng._check(self.lib.ipcfp_generated_storage_claims_copy(self.h, _p(runs) if self.n_runs else None,
+                                                                     _p(slot) if self.n else None, _p(value) if self.n else None,
+                                                                     _p(cflags) if self.n else None), "generated_storage_claims_copy")
+        return runs, slot, value, cflags
+
+    def proofs(self):
+        """→ (address of ipcfp_storage_proof_t[n], n): the reference's strings, owned by the handle (valid until close()).
+        EngineError with `.rc` / `.bad_index`: IPCFP_E_INVALID at the first failing spec, IPCFP_E_UNSUPPORTED at the first
+        proof with a folded CID."""
+        p, n, bad = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        rc = self.lib.ipcfp_generated_storage_claims_proofs(self.h, C.byref(p), C.byref(n), C.byref(bad))
+        if rc != 0:
+            msg = self.lib.ipcfp_last_error(self.eng.h)
+            e = EngineError(f"generated_storage_claims_proofs: {msg.decode() if msg else ''} ({rc})")
+            e.rc, e.bad_index = rc, int(bad.value)
+            raise e
+        return (p.value or 0), int(n.value)
+
+    def proof_rows(self):
+        return _storage_proof_rows(*self.proofs())
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self.eng.h:  # a context that is already gone took its device memory with it
+                self.lib.ipcfp_generated_storage_claims_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def bundle_check_json(text: bytes, flags: int = 0):
     """Host half of the bundle parse (no GPU): → (ok, n_storage, n_events, n_blocks, error text)."""
     lib = load_library()
@@ -1459,6 +1629,28 @@ class Witness:
                                                                _p(out), _p(wid), None, len(wid), C.byref(nb)),
                         "generate_storage_proofs")
         return out, wid[: int(nb.value)]
+
+    def generate_storage_claims(self, child_cid: bytes, child_epoch: int, actor_ids, slots32) -> "GeneratedStorageClaims":
+        """generate_storage_proof for n (actor_id, slot) specs whose proofs stay in HBM as column claims
+        (ipcfp_generate_storage_claims) → GeneratedStorageClaims (a context manager)."""
+        child = cid_slots([child_cid])[0].copy()
+        ids_in = np.ascontiguousarray(actor_ids, dtype=np.uint64)
+        slots = np.ascontiguousarray(slots32, dtype=np.uint8).reshape(-1, 32)
+        n = len(ids_in)
+        h = C.c_void_p()
+        self.eng._check(self.lib.ipcfp_generate_storage_claims(self.eng.h, self.h, _p(child), int(child_epoch), _p(ids_in) if n else None,
+                                                               _p(slots) if n else None, n, C.byref(h)), "generate_storage_claims")
+        return GeneratedStorageClaims(self.eng, h)
+
+    def generate_storage_claims_device(self, child_cid: bytes, child_epoch: int, actor_ids_ptr: int, slots_ptr: int,
+                                       n: int) -> "GeneratedStorageClaims":
+        """The same with the specs resident in HBM: actor ids u64[n], slots u8[n][32] on a 16-byte boundary."""
+        child = cid_slots([child_cid])[0].copy()
+        h = C.c_void_p()
+        self.eng._check(self.lib.ipcfp_generate_storage_claims_device(self.eng.h, self.h, _p(child), int(child_epoch),
+                                                                      actor_ids_ptr or None, slots_ptr or None, int(n), C.byref(h)),
+                        "generate_storage_claims_device")
+        return GeneratedStorageClaims(self.eng, h)
 
     # -- verifiers (claim arrays are ctypes arrays of the ipcfp.h structs) -------------------
     def verify_storage_proofs(self, claims_arr, n, trust=None):

@@ -4,6 +4,7 @@
 //
 //   ipcfp_generate_event_proofs    src/proofs/events/generator.rs:75-178  (+ :180-307 via the scan)
 //   ipcfp_generate_storage_proofs  src/proofs/storage/generator.rs:29-69
+//   ipcfp_generate_storage_claims  src/proofs/storage/generator.rs:29-178, as column claims in HBM (kernels/storage_claims_gen.hip)
 //
 // The reference runs against an RPC blockstore and records every block it loads in a
 // `RecordingBlockStore`; here the blockstore is the HBM-resident witness (the blocks a
@@ -19,7 +20,9 @@
 #include "../common.h"
 #include "../kernels/amt_enum.h"
 #include "../kernels/claims_dev.h"
+#include "../kernels/hamt_table.h"
 #include "../kernels/launch.h"
+#include "../kernels/storage_runs.h"
 #include "exec_state.h"
 #include "tipset_wide.h"
 
@@ -607,6 +610,316 @@ int ipcfp_generate_proof_bundle(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint
         if (witness_block_ids) witness_block_ids[i] = all_ids[perm[i]];
         if (witness_cids40) std::memcpy(witness_cids40 + i * IPCFP_CID_SLOT, cids.data() + size_t(perm[i]) * IPCFP_CID_SLOT, IPCFP_CID_SLOT);
     }
+    return IPCFP_OK;
+}
+
+}  // extern "C"
+
+// ---- generate_storage_proof finished as column claims in HBM (include/ipcfp.h; kernels/storage_claims_gen.hip) --------------
+
+// The handle of ipcfp_generate_storage_claims*: run table, columns and status bytes in HBM, everything else on the host.
+struct ipcfp_generated_storage_claims {
+    ipcfp_ctx* ctx = nullptr;
+    uint64_t n = 0;
+    uint32_t n_runs = 0;
+    DevBuf<uint8_t> runs_d, slot_d, value_d, cflags_d, status_d;
+    std::vector<uint32_t> block_ids;
+    // host copies, made on first use
+    bool have_host = false;
+    std::vector<uint8_t> runs_h, slot_h, value_h, cflags_h, status_h;
+    uint64_t first_error = ~0ull;
+    std::vector<ipcfp_storage_claim_t> rows_h;
+    ipcfp_unpacked_storage_t* unpacked = nullptr;
+};
+
+namespace {
+
+int sgen_host_copy(ipcfp_generated_storage_claims* g) {
+    if (g->have_host) return IPCFP_OK;
+    ipcfp_ctx* ctx = g->ctx;
+    IPCFP_ENTER(ctx);
+    g->runs_h.resize(size_t(g->n_runs) * IPCFP_SRUN_BYTES);
+    g->slot_h.resize(g->n * 32);
+    g->value_h.resize(g->n * 32);
+    g->cflags_h.resize(g->n);
+    g->status_h.resize(g->n);
+    if (g->n) {
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->runs_h.data(), g->runs_d.p, g->runs_h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->slot_h.data(), g->slot_d.p, g->slot_h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->value_h.data(), g->value_d.p, g->value_h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->cflags_h.data(), g->cflags_d.p, g->cflags_h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->status_h.data(), g->status_d.p, g->status_h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    }
+    g->first_error = ~0ull;
+    for (uint64_t i = 0; i < g->n; ++i)
+        if (g->status_h[i] != IPCFP_ST_TRUE) {
+            g->first_error = i;
+            break;
+        }
+    g->have_host = true;
+    return IPCFP_OK;
+}
+
+// The specs are in HBM (actor_d, slot_d); `own_slots` (nullable): a buffer of the call's own that already holds the slot
+// column and becomes the handle's, else the column is copied.
+int generate_storage_claims_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint8_t* child_cid40, int64_t child_epoch, const uint64_t* actor_d,
+                                 const uint8_t* slot_d, uint64_t n64, DevBuf<uint8_t>* own_slots, ipcfp_generated_storage_claims_t** out) {
+    std::unique_ptr<ipcfp_generated_storage_claims, void (*)(ipcfp_generated_storage_claims*)> g(
+        new (std::nothrow) ipcfp_generated_storage_claims(), ipcfp_generated_storage_claims_destroy);
+    if (!g) return set_error(ctx, IPCFP_E_NOMEM, "generate_storage_claims: out of memory");
+    g->ctx = ctx;
+    g->n = n64;
+    if (n64 == 0) {
+        g->have_host = true;
+        *out = g.release();
+        return IPCFP_OK;
+    }
+    const uint32_t n = uint32_t(n64);
+    const CidKey child = key_from_slot(child_cid40);
+    const uint32_t words = div_up(uint32_t(wit->n), 32);
+    DevBuf<uint32_t> touched;
+    IPCFP_HIP(ctx, touched.alloc(words));
+    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words) * 4, ctx->stream));
+    const WitnessView rec = witness_view(wit, touched.p);  // the recorder: every kernel below that fetches a block gets this view
+    const WitnessView plain = witness_view(wit);
+    // the verifier's rule (host/verify_storage.cpp): the node table pays for itself when the batch is large against the witness
+    const int forced = ctx->hamt_table;
+    const bool tabled = forced == 1 || (forced != 0 && n64 * 16u >= wit->n);
+    if (own_slots) {
+        g->slot_d.swap(*own_slots);
+    } else {
+        IPCFP_HIP(ctx, g->slot_d.alloc(n64 * 32));
+        IPCFP_HIP(ctx, hipMemcpyAsync(g->slot_d.p, slot_d, n64 * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    IPCFP_HIP(ctx, g->value_d.alloc(n64 * 32));
+    IPCFP_HIP(ctx, g->cflags_d.alloc(n64));
+    IPCFP_HIP(ctx, g->status_d.alloc(n64));
+    constexpr uint32_t kUndecided = 0xfdu;
+    constexpr uint32_t kTableKinds = HK_ACTOR_STATE | HK_VEC_U8;
+    DevBuf<HamtNodeRec> table;
+    DevBuf<uint32_t> long_list, long_count, flag, pos, run_of;
+    DevBuf<uint64_t> scratch, total_d;
+    DevBuf<StorageRun> runs;
+    // The node table is the verifier's, made the way verify_storage_impl makes it (same kernels, same placement: the lane
+    // kernel on the aux stream, the 32-lane outline of the long blocks on the K1 stream, the main stream discovering the
+    // runs and walking their chain meanwhile); the guards drain the side streams before the buffers above go back to the pool.
+    const bool side = tabled && ctx->stream_aux != ctx->stream && ctx->aux_event && ctx->main_event;
+    const bool side2 = side && ctx->stream_k1 != ctx->stream && ctx->stream_k1 != ctx->stream_aux;
+    StreamDrainGuard aux_guard(ctx->stream_aux), k1_guard(ctx->stream_k1);
+    int rc = IPCFP_OK;
+    if (tabled) {
+        IPCFP_HIP(ctx, table.alloc(wit->n));
+        IPCFP_HIP(ctx, long_list.alloc(wit->n));
+        IPCFP_HIP(ctx, long_count.alloc(1));
+        IPCFP_HIP(ctx, hipMemsetAsync(long_count.p, 0, 4, ctx->stream));
+        rc = launch_hamt_list_long(ctx, wit->k1_meta.p, uint32_t(wit->n), long_list.p, long_count.p);
+        if (rc) return rc;
+        if (side) {
+            IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));
+            IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
+            aux_guard.armed = true;
+            hipStream_t saved = ctx->stream;
+            ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
+            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
+            ctx->stream = saved;
+        } else {
+            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
+        }
+        if (rc) return rc;
+    }
+    // run discovery: one lane per spec, the prefix sum, and the number of runs with the call's one synchronisation
+    IPCFP_HIP(ctx, flag.alloc(n));
+    IPCFP_HIP(ctx, pos.alloc(n));
+    IPCFP_HIP(ctx, run_of.alloc(n));
+    IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
+    IPCFP_HIP(ctx, total_d.alloc(1));
+    rc = launch_sgen_run_flags(ctx, actor_d, n, flag.p);
+    if (rc) return rc;
+    {
+        ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
+        rc = launch_scan_u32(ctx, flag.p, n, pos.p, total_d.p, scratch.p);
+    }
+    if (rc) return rc;
+    uint64_t n_runs = 0;
+    uint32_t n_long = 0;
+    IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
+    if (tabled) IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    if (n_runs == 0 || n_runs > n) return set_error(ctx, IPCFP_E_INVALID, "generate_storage_claims: %llu runs of %u specs", (unsigned long long)n_runs, n);
+    hipEvent_t outline_done = nullptr;
+    if (n_long) {
+        hipStream_t s = ctx->stream;
+        if (side2) {
+            s = ctx->stream_k1;
+            k1_guard.armed = true;
+            IPCFP_HIP(ctx, hipStreamWaitEvent(s, ctx->main_event, 0));
+        } else if (ctx->stream_aux != ctx->stream && ctx->aux_event) {
+            s = ctx->stream_aux;
+            aux_guard.armed = true;
+        }
+        rc = launch_hamt_outline_list(ctx, s, plain, table.p, long_list.p, long_count.p, n_long);
+        if (!rc) rc = launch_hamt_node_table_rest(ctx, s, plain, long_list.p, long_count.p, n_long, kTableKinds, table.p);
+        if (rc) return rc;
+        if (s == ctx->stream_k1) {
+            if (!ctx->outline_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&ctx->outline_event, hipEventDisableTiming));
+            outline_done = ctx->outline_event;
+            IPCFP_HIP(ctx, hipEventRecord(outline_done, s));
+        }
+    }
+    if (aux_guard.armed) IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
+    g->n_runs = uint32_t(n_runs);
+    IPCFP_HIP(ctx, runs.alloc(n_runs));
+    IPCFP_HIP(ctx, g->runs_d.alloc(n_runs * IPCFP_SRUN_BYTES));
+    {
+        ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
+        rc = launch_storage_run_heads(ctx, flag.p, pos.p, n, run_of.p, runs.p);
+    }
+    if (rc) return rc;
+    rc = launch_sgen_run_chain(ctx, rec, child, runs.p, uint32_t(n_runs), kUndecided);
+    if (rc) return rc;
+    // the table is whole from here on
+    if (aux_guard.armed) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_event, 0));
+    if (outline_done) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_done, 0));
+    aux_guard.armed = k1_guard.armed = false;  // the main stream is ordered behind the side kernels now
+    rc = launch_sgen_run_actors(ctx, rec, tabled ? table.p : nullptr, actor_d, runs.p, uint32_t(n_runs), kUndecided);
+    if (!rc) rc = launch_sgen_run_state(ctx, rec, runs.p, uint32_t(n_runs));
+    DevBuf<uint32_t> root_children;  // block of every run's storage root, then the blocks behind its 32 links
+    if (tabled) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 33u));
+    if (!rc)
+        rc = launch_sgen_specs(ctx, rec, tabled ? table.p : nullptr, g->slot_d.p, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p,
+                               g->value_d.p, g->cflags_d.p, g->status_d.p);
+    if (!rc) rc = launch_sgen_run_records(ctx, runs.p, uint32_t(n_runs), n, child, child_epoch, actor_d, g->runs_d.p);
+    // the recorded blocks in BTreeSet order (synchronises: the columns are whole when it returns)
+    uint64_t nb = 0;
+    if (!rc) {
+        g->block_ids.resize(wit->n ? wit->n : 1);
+        rc = materialize(ctx, wit, touched.p, g->block_ids.data(), nullptr, g->block_ids.size(), &nb);
+    }
+    if (rc) {
+        (void)sync_stream(ctx, ctx->stream);
+        return rc;
+    }
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream, true));
+    g->block_ids.resize(nb);
+    *out = g.release();
+    return IPCFP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ipcfp_generate_storage_claims_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cid40, int64_t child_epoch,
+                                         const void* actor_ids_d, const void* slots32_d, uint64_t n, ipcfp_generated_storage_claims_t** out) {
+    if (!ctx || !w || w->ctx != ctx || !child_cid40 || !out || (n && (!actor_ids_d || !slots32_d))) return IPCFP_E_INVALID;
+    *out = nullptr;
+    if (n >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "batch too large");
+    if ((reinterpret_cast<uintptr_t>(slots32_d) & 15u) || (reinterpret_cast<uintptr_t>(actor_ids_d) & 7u))
+        return set_error(ctx, IPCFP_E_INVALID, "generate_storage_claims_device: the slot column must lie on a 16-byte boundary, the actor ids on an 8-byte one");
+    IPCFP_ENTER(ctx);
+    return generate_storage_claims_impl(ctx, w, child_cid40, child_epoch, static_cast<const uint64_t*>(actor_ids_d),
+                                        static_cast<const uint8_t*>(slots32_d), n, nullptr, out);
+}
+
+int ipcfp_generate_storage_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cid40, int64_t child_epoch,
+                                  const uint64_t* actor_ids, const uint8_t* slots32, uint64_t n, ipcfp_generated_storage_claims_t** out) {
+    if (!ctx || !w || w->ctx != ctx || !child_cid40 || !out || (n && (!actor_ids || !slots32))) return IPCFP_E_INVALID;
+    *out = nullptr;
+    if (n >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "batch too large");
+    IPCFP_ENTER(ctx);
+    DevBuf<uint64_t> actor_d;
+    DevBuf<uint8_t> slot_d;
+    if (n) {
+        IPCFP_HIP(ctx, actor_d.alloc(n));
+        IPCFP_HIP(ctx, slot_d.alloc(n * 32));
+        IPCFP_HIP(ctx, hipMemcpyAsync(actor_d.p, actor_ids, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(slot_d.p, slots32, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const uint8_t* slots_p = slot_d.p;
+    const int rc = generate_storage_claims_impl(ctx, w, child_cid40, child_epoch, actor_d.p, slots_p, n, n ? &slot_d : nullptr, out);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's memory)
+    return rc;
+}
+
+void ipcfp_generated_storage_claims_destroy(ipcfp_generated_storage_claims_t* g) {
+    if (!g) return;
+    if (g->unpacked) ipcfp_unpacked_storage_destroy(g->unpacked);
+    delete g;
+}
+uint64_t ipcfp_generated_storage_claims_count(const ipcfp_generated_storage_claims_t* g) { return g ? g->n : 0; }
+uint32_t ipcfp_generated_storage_claims_run_count(const ipcfp_generated_storage_claims_t* g) { return g ? g->n_runs : 0; }
+const void* ipcfp_generated_storage_claims_runs_device(const ipcfp_generated_storage_claims_t* g) { return g ? g->runs_d.p : nullptr; }
+const void* ipcfp_generated_storage_claims_slots_device(const ipcfp_generated_storage_claims_t* g) { return g ? g->slot_d.p : nullptr; }
+const void* ipcfp_generated_storage_claims_values_device(const ipcfp_generated_storage_claims_t* g) { return g ? g->value_d.p : nullptr; }
+const void* ipcfp_generated_storage_claims_cflags_device(const ipcfp_generated_storage_claims_t* g) { return g ? g->cflags_d.p : nullptr; }
+const void* ipcfp_generated_storage_claims_status_device(const ipcfp_generated_storage_claims_t* g) { return g ? g->status_d.p : nullptr; }
+const uint8_t* ipcfp_generated_storage_claims_status(ipcfp_generated_storage_claims_t* g, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || sgen_host_copy(g)) return nullptr;
+    if (n) *n = g->n;
+    return g->status_h.data();
+}
+uint64_t ipcfp_generated_storage_claims_first_error(ipcfp_generated_storage_claims_t* g) {
+    if (!g || sgen_host_copy(g)) return ~0ull;
+    return g->first_error;
+}
+int ipcfp_generated_storage_claims_copy(ipcfp_generated_storage_claims_t* g, uint8_t* runs_out, uint8_t* slots_out, uint8_t* values_out,
+                                        uint8_t* cflags_out) {
+    if (!g) return IPCFP_E_INVALID;
+    if (const int rc = sgen_host_copy(g)) return rc;
+    if (runs_out && !g->runs_h.empty()) std::memcpy(runs_out, g->runs_h.data(), g->runs_h.size());
+    if (slots_out && g->n) std::memcpy(slots_out, g->slot_h.data(), g->slot_h.size());
+    if (values_out && g->n) std::memcpy(values_out, g->value_h.data(), g->value_h.size());
+    if (cflags_out && g->n) std::memcpy(cflags_out, g->cflags_h.data(), g->cflags_h.size());
+    return IPCFP_OK;
+}
+const uint32_t* ipcfp_generated_storage_claims_block_ids(const ipcfp_generated_storage_claims_t* g, uint64_t* n) {
+    if (n) *n = g ? g->block_ids.size() : 0;
+    return g ? g->block_ids.data() : nullptr;
+}
+int ipcfp_generated_storage_claims_proofs(ipcfp_generated_storage_claims_t* g, const ipcfp_storage_proof_t** proofs, uint64_t* n,
+                                          uint64_t* bad_index) {
+    if (!g || !proofs || !n) return IPCFP_E_INVALID;
+    *proofs = nullptr;
+    *n = 0;
+    if (bad_index) *bad_index = ~0ull;
+    if (!g->unpacked) {
+        if (const int rc = sgen_host_copy(g)) return rc;
+        if (g->first_error != ~0ull) {  // `generate_storage_proof(..).await?` (generator.rs:48-49): there is no bundle
+            if (bad_index) *bad_index = g->first_error;
+            return set_error(g->ctx, IPCFP_E_INVALID, "generated_storage_claims_proofs: spec %llu failed with status %u",
+                             (unsigned long long)g->first_error, unsigned(g->status_h[g->first_error]));
+        }
+        // the host copy expanded to rows (ipcfp_expand_storage_claims' loop over a form this file made itself)
+        try {
+            g->rows_h.resize(g->n);
+        } catch (...) {
+            return set_error(g->ctx, IPCFP_E_NOMEM, "generated_storage_claims_proofs: out of memory");
+        }
+        for (uint32_t r = 0; r < g->n_runs; ++r) {
+            const uint8_t* rec = g->runs_h.data() + size_t(r) * IPCFP_SRUN_BYTES;
+            uint32_t tail[4];
+            std::memcpy(tail, rec + IPCFP_SRUN_OFF_FIRST_CLAIM, sizeof tail);
+            if (uint64_t(tail[0]) + tail[1] > g->n) return set_error(g->ctx, IPCFP_E_INVALID, "generated_storage_claims_proofs: run %u does not lie in the batch", r);
+            for (uint64_t i = tail[0], e = uint64_t(tail[0]) + tail[1]; i < e; ++i) {
+                ipcfp_storage_claim_t& c = g->rows_h[i];
+                std::memcpy(&c, rec, IPCFP_SRUN_OFF_FIRST_CLAIM);
+                std::memcpy(c.slot, g->slot_h.data() + 32 * i, 32);
+                std::memcpy(c.value, g->value_h.data() + 32 * i, 32);
+                c.flags = tail[2] | g->cflags_h[i];
+                c.reserved = tail[3];
+            }
+        }
+        uint64_t bad = ~0ull;
+        const int rc = ipcfp_unpack_storage_claims(g->rows_h.data(), g->n, &g->unpacked, &bad);
+        if (bad_index) *bad_index = bad;
+        if (rc == IPCFP_E_UNSUPPORTED)
+            return set_error(g->ctx, rc, "generated_storage_claims_proofs: a CID of proof %llu is longer than the %d-byte slot and the claim keeps only its fold",
+                             (unsigned long long)bad, int(IPCFP_CID_SLOT));
+        if (rc) return set_error(g->ctx, rc, "generated_storage_claims_proofs: claim %llu does not unpack", (unsigned long long)bad);
+    }
+    *proofs = ipcfp_unpacked_storage_proofs(g->unpacked, n);
     return IPCFP_OK;
 }
 

@@ -8,6 +8,9 @@
 // in the shape of pack_claims.cpp and bundle_write.cpp: the tipsets' strings in one sequential pass (there are a handful),
 // then contiguous claim ranges on run_parts threads — each range is checked and sized, then written at its place in ONE
 // character arena.  IPCFP_HOST_THREADS=k pins the number of ranges.
+//
+// ipcfp_unpack_storage_claims is the same for `StorageProof` (src/proofs/storage/bundle.rs:5-14) as create_proof_claim spells
+// it (src/proofs/storage/generator.rs:158-178): four `Cid::to_string()`s, slot and value `format!("0x{}", hex::encode(..))`.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -219,5 +222,111 @@ const ipcfp_event_proof_t* ipcfp_unpacked_events_proofs(const ipcfp_unpacked_eve
 }
 
 void ipcfp_unpacked_events_destroy(ipcfp_unpacked_events_t* u) { delete u; }
+
+}  // extern "C"
+
+// ---- packed storage claims → StorageProof structs ---------------------------------------------------------------------------
+
+struct ipcfp_unpacked_storage {
+    std::vector<ipcfp_storage_proof_t> proofs;
+    std::vector<char> chars;  // the six strings of every proof, NUL-terminated
+};
+
+extern "C" {
+
+int ipcfp_unpack_storage_claims(const ipcfp_storage_claim_t* claims, uint64_t n, ipcfp_unpacked_storage_t** out, uint64_t* bad_index) {
+    if (bad_index) *bad_index = kNoBad;
+    if (!out) return IPCFP_E_INVALID;
+    *out = nullptr;
+    if (n && !claims) return IPCFP_E_INVALID;
+    ipcfp_unpacked_storage* h = new (std::nothrow) ipcfp_unpacked_storage();
+    if (!h) return IPCFP_E_NOMEM;
+    struct Part {
+        uint64_t chars = 0;
+        uint64_t bad = kNoBad;
+        int rc = IPCFP_OK;
+    };
+    const unsigned T = claim_threads(n);
+    constexpr uint32_t kAll = IPCFP_SRUN_FLAG_MASK | IPCFP_SCOL_FLAG_MASK;
+    // "b" + base32 of len bytes (or base58 of a CIDv0: never longer than that), NUL
+    auto cid_chars = [](int len) { return 2 + (uint64_t(len) * 8 + 4) / 5 + 8; };
+    try {
+        std::vector<Part> part(T);
+        h->proofs.resize(n);
+        // ---- pass 1 (parallel by contiguous ranges): every claim checked and sized ----
+        auto size_work = [&](unsigned t) {
+            Part& r = part[t];
+            for (uint64_t i = n * t / T, hi = n * (t + 1) / T; i < hi; ++i) {
+                const ipcfp_storage_claim_t& c = claims[i];
+                int rc = IPCFP_OK;
+                uint64_t chars = 2 * 67;
+                if (c.flags != kAll || c.reserved != 0) rc = IPCFP_E_INVALID;  // a bit missing, or bits nobody knows
+                const uint8_t* slots[4] = {c.child, c.state_root, c.actor_state, c.storage_root};
+                for (int k = 0; k < 4 && !rc; ++k) {
+                    const int len = slot_cid_len(slots[k]);
+                    if (len < 0) rc = IPCFP_E_UNSUPPORTED;
+                    else if (len == 0) rc = IPCFP_E_INVALID;
+                    else chars += cid_chars(len);
+                }
+                if (rc) {
+                    r.bad = i, r.rc = rc;
+                    return;
+                }
+                r.chars += chars;
+            }
+        };
+        if (!run_parts(T, size_work)) throw std::bad_alloc();
+        for (const Part& r : part)
+            if (r.bad != kNoBad) {  // ranges are in claim order: the first range with a refusal holds the lowest claim
+                if (bad_index) *bad_index = r.bad;
+                const int rc = r.rc;
+                delete h;
+                return rc;
+            }
+        // ---- pass 2: one arena, every range writes at its own place ----
+        std::vector<uint64_t> c_at(T + 1, 0);
+        for (unsigned t = 0; t < T; ++t) c_at[t + 1] = c_at[t] + part[t].chars;
+        h->chars.resize(c_at[T] + 1);
+        auto write_work = [&](unsigned t) {
+            char* o = h->chars.data() + c_at[t];
+            auto put_cid = [&](const uint8_t* slot) {
+                const std::string s = cid_to_string(slot, size_t(slot_cid_len(slot)));
+                std::memcpy(o, s.c_str(), s.size() + 1);
+                const char* at = o;
+                o += s.size() + 1;
+                return at;
+            };
+            for (uint64_t i = n * t / T, hi = n * (t + 1) / T; i < hi; ++i) {
+                const ipcfp_storage_claim_t& c = claims[i];
+                ipcfp_storage_proof_t& p = h->proofs[i];
+                p.child_epoch = c.child_epoch;
+                p.actor_id = c.actor_id;
+                p.child_block_cid = put_cid(c.child);
+                p.parent_state_root = put_cid(c.state_root);
+                p.actor_state_cid = put_cid(c.actor_state);
+                p.storage_root = put_cid(c.storage_root);
+                hex0x(c.slot, 32, o);
+                p.slot = o;
+                o += 67;
+                hex0x(c.value, 32, o);
+                p.value = o;
+                o += 67;
+            }
+        };
+        if (!run_parts(T, write_work)) throw std::bad_alloc();
+    } catch (...) {
+        delete h;
+        return IPCFP_E_NOMEM;
+    }
+    *out = h;
+    return IPCFP_OK;
+}
+
+const ipcfp_storage_proof_t* ipcfp_unpacked_storage_proofs(const ipcfp_unpacked_storage_t* u, uint64_t* n) {
+    if (n) *n = u ? u->proofs.size() : 0;
+    return u ? u->proofs.data() : nullptr;
+}
+
+void ipcfp_unpacked_storage_destroy(ipcfp_unpacked_storage_t* u) { delete u; }
 
 }  // extern "C"

@@ -234,6 +234,27 @@ int launch_gather_keys(ipcfp_ctx* ctx, const CidKey* table_d, uint64_t table_len
                        CidKey* out_d, uint32_t* oor_d);
 int launch_gather_block_cids(ipcfp_ctx* ctx, const uint8_t* cids_d, const uint32_t* ids_d, uint32_t n, CidKey* out_d);
 
+// --- storage_claims_gen.hip --- generate_storage_proof as column claims, over runs of specs with equal actor_id
+// (ipcfp_generate_storage_claims*, host/generate.cpp).  `w` of a kernel that fetches blocks: the RECORDING view.
+// flag_d[t] = 1 where a run starts (then launch_scan_u32 and launch_storage_run_heads: run_of_d, StorageRun::first_claim)
+int launch_sgen_run_flags(ipcfp_ctx* ctx, const uint64_t* actor_id_d, uint32_t n, uint32_t* flag_d);
+// child header → parent_state_root → StateRoot.actors; actor_status = `undecided` where the actor get is due
+int launch_sgen_run_chain(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& child, void* runs_d, uint32_t n_runs, uint32_t undecided);
+// the actor get: over the node table (table_d, nullable), then the walker for every run still undecided
+int launch_sgen_run_actors(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const uint64_t* actor_id_d, void* runs_d,
+                           uint32_t n_runs, uint32_t undecided);
+// EVM state behind the derived actor-state CID, layout sniff of the derived contract_state
+int launch_sgen_run_state(ipcfp_ctx* ctx, const WitnessView& w, void* runs_d, uint32_t n_runs);
+// value_d[32 t], cflags_d[t], status_d[t] of every spec: with a table (table_d, nullable) the first step of every run's get
+// resolved once (root_children_d: n_runs × 33 words of scratch) and the table kernel, then the one-lane kernel for what that
+// left pending — or for every spec
+int launch_sgen_specs(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d, const uint8_t* slot_d, uint32_t n, const uint32_t* run_of_d,
+                      const void* runs_d, uint32_t n_runs, uint32_t* root_children_d, uint8_t* value_d, uint8_t* cflags_d,
+                      uint8_t* status_d);
+// out_d: n_runs records of IPCFP_SRUN_BYTES
+int launch_sgen_run_records(ipcfp_ctx* ctx, const void* runs_d, uint32_t n_runs, uint32_t n, const CidKey& child, long long child_epoch,
+                            const uint64_t* actor_id_d, void* out_d);
+
 // --- shard.hip ---
 int launch_plan_receipts(ipcfp_ctx* ctx, const WitnessView& rec, const CidKey& receipts_root, uint64_t lo, uint32_t n);
 int launch_plan_receipts_all(ipcfp_ctx* ctx, const WitnessView& rec, const CidKey& receipts_root, uint32_t n,

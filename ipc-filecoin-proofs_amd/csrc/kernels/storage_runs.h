@@ -30,7 +30,8 @@ struct StorageRun {
     CidKey contract_state;       // EvmState.contract_state
     CidKey hamt_root;
     uint32_t hamt_bw;
-    uint32_t pad;
+    uint32_t chain_status;       // the GENERATOR's word (storage_claims_gen.hip): TRUE when contract_state is known, else the ERR_* of
+                                 // the chain; the verifier's run kernels neither write nor read it
 };
 
 // ---- where the claims come from ---------------------------------------------------------------------------------------
