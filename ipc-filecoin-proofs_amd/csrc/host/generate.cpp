@@ -163,7 +163,7 @@ int generate_events_core(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent
     DevBuf<TipsetCtxDev> tc_d;
     IPCFP_HIP(ctx, tc_d.alloc(1));
     IPCFP_HIP(ctx, hipMemcpyAsync(tc_d.p, &tc, sizeof tc, hipMemcpyHostToDevice, ctx->stream));
-    int rc = launch_ctx_headers(ctx, rec, tc_d.p, 1);
+    int rc = launch_ctx_headers(ctx, rec, tc_d.p);
     if (rc) return rc;
     IPCFP_HIP(ctx, d2h_small(ctx, &tc, tc_d.p, sizeof tc, ctx->stream));
     IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));

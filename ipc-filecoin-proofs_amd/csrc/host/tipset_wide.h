@@ -3,8 +3,8 @@
 // The reference takes any tipset key (src/proofs/events/verifier.rs:147-181 compares `child_hdr.parents` with the claimed
 // list whatever its length, src/proofs/events/utils.rs:16-30 walks every parent header).  Keys of up to IPCFP_MAX_PARENTS
 // blocks — every key a chain has produced — travel inline (TipsetCtxDev::parents, kernel arguments).  A longer key is kept
-// whole in HBM (TipsetCtxDev::parents_wide) and such a context takes the general route: k_tipset_prepare_wide / k_exec_roots
-// with one workgroup per parent block, the level-by-level enumerator (the dense walk plans at most kMaxDenseRoots trees).
+// whole in HBM (TipsetCtxDev::parents_wide) and such a context takes the general route: k_tipset_prepare_one
+// (launch_tipset_prepare_wide / launch_exec_roots) with one workgroup per parent block, the level-by-level enumerator (the dense walk plans at most kMaxDenseRoots trees).
 #pragma once
 #include <cstring>
 #include <memory>

@@ -146,7 +146,7 @@ int verify_packed(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& t
         IPCFP_HIP(ctx, h2d_small(ctx, jobs_d.p, narrow.data(), narrow.size() * sizeof(PrepareJob), ctx->stream));
     }
     rc = launch_tipset_prepare(ctx, view, narrow.data(), jobs_d.p, uint32_t(narrow.size()),
-                               /*need_general=*/uint64_t(w->max_block_len) + 32u > uint64_t(kPrologueStageChunks) * 16u);
+                               /*need_general=*/prologue_needs_general(w->max_block_len));
     if (rc) return rc;
     // the header facts come back with the first synchronisation below (the enumerator's), not one of their own
     std::vector<TipsetCtxDev> facts(tcs.size());
@@ -448,7 +448,7 @@ int ipcfp_verify_and_scan_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const ipc
         DevBuf<TipsetCtxDev> tc_d;
         IPCFP_HIP(ctx, tc_d.alloc(1));
         IPCFP_HIP(ctx, h2d_small(ctx, tc_d.p, one.data(), sizeof(TipsetCtxDev), ctx->stream));
-        int rc = launch_ctx_headers(ctx, view, tc_d.p, 1);
+        int rc = launch_ctx_headers(ctx, view, tc_d.p);
         if (rc) return rc;
         IPCFP_HIP(ctx, d2h_small(ctx, one.data(), tc_d.p, sizeof(TipsetCtxDev), ctx->stream));
         IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));

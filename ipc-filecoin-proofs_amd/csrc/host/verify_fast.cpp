@@ -11,7 +11,7 @@
 //     lying count, a missing block, a decode error — the call's results are thrown away and verify_packed does the
 //     whole batch again its own way (the general level-synchronous walk orders errors as the reference does);
 //   * what the host did between the second wait and the verify kernel (is the execution order reachable, where are the
-//     tables, exec_len, the inverse permutation) happens on the device (k_ctx_finish).
+//     tables, exec_len, the inverse permutation) happens on the device (k_exec_scan_finish).
 // The call synchronises once.  Same kernels otherwise, same results: tests/test_gpu_events.py, test_gpu_baseline_sizes.py,
 // test_gpu_enum_shapes.py (every shape that leaves the dense path) run through this file first.
 #include <chrono>
@@ -74,7 +74,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     int rc = ctx->has_scan_hint ? block_table_prefetch(ctx, w, &ctx->scan_hint.filter, int(ctx->scan_hint.has_actor), ctx->scan_hint.actor)
                                 : block_table_prefetch(ctx, w, nullptr, 0, 0);
     if (rc) return rc;
-    const bool need_general = uint64_t(w->max_block_len) + 32u > uint64_t(kPrologueStageChunks) * 16u;
+    const bool need_general = prologue_needs_general(w->max_block_len);
     // The context on the device: a slice of the control block's ZERO half when there is room (re-initialised at the end of
     // the previous call) — its inputs then travel as a kernel argument of the prologue, which writes them in; no copy
     // kernel at the head of the call (17.7 µs beside the side streams' grids: profiles/r03_last_commit_timeline.txt).

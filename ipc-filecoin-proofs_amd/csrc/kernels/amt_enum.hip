@@ -10,8 +10,7 @@
 #include "blake2b_dev.h"
 #include "event_table.h"
 #include "launch.h"
-#include "tipset_ctx.h"
-#include "txmeta_dev.h"
+#include "tipset_prologue_body.h"
 
 namespace ipcfp {
 
@@ -66,11 +65,7 @@ __device__ __forceinline__ void txmeta_rehash_lane(const WitnessView& w, const T
     Rd r;
     r.init(w.arena + w.off[tb], w.len[tb]);
     uint32_t o[2], l[2];
-    r.expect_array(2);
-    r.read_link(o[0], l[0]);
-    r.read_link(o[1], l[1]);
-    r.finish();
-    if (!r.ok() || l[0] > 64u || l[1] > 64u) {  // (the prologue took this very block: not reachable)
+    if (!txmeta_links(r, o[0], l[0], o[1], l[1]) || l[0] > 64u || l[1] > 64u) {  // (the prologue took this very block: not reachable)
         enum_error(err, seq, 0, IPCFP_ST_ERR_DECODE);
         return;
     }

@@ -31,8 +31,6 @@ int launch_expand_cids(ipcfp_ctx* ctx, const uint8_t* digests32_d, uint32_t n, c
 // dst[new_off[i] .. +len[i]) = src[old_off[i] .. +len[i]); pad bytes up to the next 16 are zeroed.
 int launch_repack(ipcfp_ctx* ctx, const uint8_t* src, const uint64_t* old_off, const uint32_t* len,
                   const uint64_t* new_off, uint32_t n, uint8_t* dst);
-// *flag_d |= 1 if any off[i] % 16 != 0
-int launch_check_aligned(ipcfp_ctx* ctx, const uint64_t* off_d, uint32_t n, uint32_t* flag_d);
 
 // --- hash_short.hip (K2 Keccak-256, K3 SHA-256) ---
 int launch_keccak256(ipcfp_ctx* ctx, const uint8_t* bytes, const uint64_t* off, const uint32_t* len, uint32_t n,
@@ -136,15 +134,14 @@ struct EventRec;
 struct EventTableView;
 struct LeafRef;
 struct EventClaimPacked;
-int launch_ctx_headers(ipcfp_ctx* ctx, const WitnessView& w, TipsetCtxDev* ctxs_d, uint32_t n);  // tipset_prepare_general.hip
+// the header facts of ONE context (tipset_prepare_general.hip; the tipset prologue below is the whole of it)
+int launch_ctx_headers(ipcfp_ctx* ctx, const WitnessView& w, TipsetCtxDev* ctx_d);
 struct CtxFinish;
-int launch_ctx_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a);
 // the flags' prefix sum (decoupled look-back), positions (pos_d), inverse, total (total_d) and the context's tail in one
 // launch, the flags ready in a.first; ctl_d: exec_scan_ctl_words(a.raw_len) words that are zero when it is queued
 int launch_exec_scan_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* pos_d, uint64_t* total_d,
                             unsigned long long* ctl_d);
 size_t exec_scan_ctl_words(uint32_t n);
-int launch_exec_insert(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, unsigned long long* slots_d, uint32_t mask);
 int launch_exec_insert_flags(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, unsigned long long* slots_d, uint32_t mask,
                              uint32_t* first_d);
 int launch_exec_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const uint64_t* total_d, const uint32_t* first_d,

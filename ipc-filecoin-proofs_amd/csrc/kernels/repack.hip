@@ -123,12 +123,6 @@ __global__ __launch_bounds__(256) void k_repack(const uint8_t* __restrict__ src,
     }
 }
 
-__global__ void k_check_aligned(const uint64_t* __restrict__ off, uint32_t n, uint32_t* __restrict__ flag) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool bad = i < n && (off[i] & 15ull) != 0;
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
-}
-
 template <bool PAD>
 static int launch_offsets(ipcfp_ctx* ctx, const uint32_t* len_d, uint32_t n, uint64_t* new_off_d, uint64_t* total_d,
                           uint64_t* scratch_d) {
@@ -205,13 +199,6 @@ int launch_repack(ipcfp_ctx* ctx, const uint8_t* src, const uint64_t* old_off, c
     const uint32_t groups = n < 8192u * 8u ? n : 8192u * 8u;  // half-wavefronts
     hipLaunchKernelGGL(k_repack, dim3(div_up(groups, 8)), dim3(256), 0, ctx->stream, src, old_off, len, new_off, n,
                        dst);
-    IPCFP_HIP(ctx, hipGetLastError());
-    return IPCFP_OK;
-}
-
-int launch_check_aligned(ipcfp_ctx* ctx, const uint64_t* off_d, uint32_t n, uint32_t* flag_d) {
-    if (n == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_check_aligned, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, off_d, n, flag_d);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }

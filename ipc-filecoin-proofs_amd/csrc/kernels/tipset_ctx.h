@@ -28,7 +28,7 @@ struct TipsetCtxDev {
     uint32_t n_parents;
     CidKey child;
     CidKey parents[IPCFP_MAX_PARENTS];
-    // header facts (k_ctx_headers)
+    // header facts (tipset_prologue_body.h prologue_headers)
     uint32_t child_status;     // TRUE or ERR_* of `get(child)` + HeaderLite decode
     uint32_t parents_match;    // child_hdr.parents == parent_cids
     long long child_height;
@@ -37,8 +37,8 @@ struct TipsetCtxDev {
     uint32_t pad0;
     unsigned long long prologue_general;  // bit s: slot s of the tipset prologue is left to the general kernel (a block larger than the LDS stage)
     long long parent0_height;
-    // 1 + the TxMeta block of parent b when its re-hash was LEFT to k_txmeta_rehash (amt_enum.hip; tipset_prepare.hip
-    // roots_slot with `defer_rehash`); 0: nothing to re-hash (checked inline, or never reached) — so that a context
+    // 1 + the TxMeta block of parent b when its re-hash was LEFT to k_txmeta_rehash (amt_enum.hip; tipset_prologue_body.h
+    // prologue_roots with kTxMetaDefer); 0: nothing to re-hash (checked inline, or never reached) — so that a context
     // taken from zeroed memory needs no initialisation.
     uint32_t txmeta_block[IPCFP_MAX_PARENTS];
     // A tipset key of MORE than IPCFP_MAX_PARENTS blocks (the reference takes any: src/proofs/events/verifier.rs:147-181,
@@ -71,7 +71,7 @@ __device__ __forceinline__ CidKey tipset_parent(const TipsetCtxDev& c, uint32_t 
     return c.parents_wide ? c.parents_wide[b] : c.parents[b < IPCFP_MAX_PARENTS ? b : 0u];
 }
 
-// what k_ctx_finish (verify_events.hip) writes into a context on the device
+// what k_exec_scan_finish (verify_events.hip) writes into a context on the device
 struct CtxFinish {
     const unsigned long long* err;   // packed first error of the execution-order reconstruction (kNoEnumError: none)
     const uint64_t* total;           // number of distinct messages
@@ -107,5 +107,9 @@ __device__ __forceinline__ PrepareJob prepare_job(const PrepareJobs& j, uint32_t
 // LDS stage of the prologue (tipset_prepare.hip): a block header is 0.6-2 KB, a TxMeta 90 bytes.  A witness whose
 // largest block fits needs no general companion launch.
 constexpr uint32_t kPrologueStageChunks = 512;  // 8 KB
+constexpr uint32_t kPrologueStageBytes = kPrologueStageChunks * 16u;
+constexpr uint32_t kPrologueStageSlack = 32u;  // the two chunks behind a block that the copy and the reader may touch
+// the kernel's fit test, asked of a witness's largest block: does the LDS prologue need its general companion?
+inline bool prologue_needs_general(uint64_t max_block_len) { return max_block_len + kPrologueStageSlack > kPrologueStageBytes; }
 
 }  // namespace ipcfp

@@ -120,6 +120,10 @@ __global__ __launch_bounds__(256) void k_exec_first(const CidKey* __restrict__ k
     first[i] = f;
 }
 
+// The tail of a tipset context ON THE DEVICE (host/verify_fast.cpp; k_exec_scan_finish below): what
+// host/verify_events.cpp::verify_packed does between its second synchronisation and the verify kernel — decide whether the
+// execution order is reachable, point the context at the tables, copy exec_len — without the host having seen the header
+// facts.  Same rules, same order.
 __device__ __forceinline__ void ctx_finish_fields(TipsetCtxDev* __restrict__ c, const CtxFinish& a, uint64_t total) {
     c->exec_status = IPCFP_ST_ERR_BAD_CLAIM;
     c->exec_slots = nullptr;
@@ -346,15 +350,6 @@ __global__ __launch_bounds__(256) void k_exec_finish(TipsetCtxDev* __restrict__ 
     if (i < n && first[i]) inv[pos[i]] = i;
 }
 
-// The tail of a tipset context ON THE DEVICE (host/verify_fast.cpp): what host/verify_events.cpp::verify_packed does between
-// its second synchronisation and the verify kernel — decide whether the execution order is reachable, point the context
-// at the tables, copy exec_len, invert exec_pos — without the host having seen the header facts.  Same rules, same order.
-__global__ __launch_bounds__(256) void k_ctx_finish(TipsetCtxDev* __restrict__ c, CtxFinish a) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < a.raw_len && a.first[i]) a.inv[a.pos[i]] = i;
-    if (i == 0) ctx_finish_fields(c, a, *a.total);
-}
-
 // ctl_d: exec_scan_ctl_words(a.raw_len) words, zero when this is queued
 int launch_exec_scan_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a, uint32_t* pos_d, uint64_t* total_d,
                             unsigned long long* ctl_d) {
@@ -366,12 +361,6 @@ int launch_exec_scan_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish
     return IPCFP_OK;
 }
 size_t exec_scan_ctl_words(uint32_t n) { return 1u + size_t(div_up(n, kExecTile)); }
-
-int launch_ctx_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const CtxFinish& a) {
-    hipLaunchKernelGGL(k_ctx_finish, dim3(a.raw_len ? div_up(a.raw_len, 256) : 1), dim3(256), 0, ctx->stream, ctx_d, a);
-    IPCFP_HIP(ctx, hipGetLastError());
-    return IPCFP_OK;
-}
 
 // ------------------------------ launchers -----------------------------------
 int launch_exec_finish(ipcfp_ctx* ctx, TipsetCtxDev* ctx_d, const uint64_t* total_d, const uint32_t* first_d,
@@ -389,13 +378,6 @@ int launch_exec_dedup(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* leave
     if (leaves_d) hipLaunchKernelGGL(k_exec_keys, g, b, 0, ctx->stream, w, leaves_d, n, keys_d);  // else: keys came with the enumeration
     hipLaunchKernelGGL(k_exec_insert, g, b, 0, ctx->stream, keys_d, n, slots_d, mask);
     hipLaunchKernelGGL(k_exec_first, g, b, 0, ctx->stream, keys_d, n, slots_d, mask, first_d);
-    IPCFP_HIP(ctx, hipGetLastError());
-    return IPCFP_OK;
-}
-
-int launch_exec_insert(ipcfp_ctx* ctx, const CidKey* keys_d, uint32_t n, unsigned long long* slots_d, uint32_t mask) {
-    if (n == 0) return IPCFP_OK;
-    hipLaunchKernelGGL(k_exec_insert, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, keys_d, n, slots_d, mask);
     IPCFP_HIP(ctx, hipGetLastError());
     return IPCFP_OK;
 }

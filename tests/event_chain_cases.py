@@ -202,6 +202,35 @@ CASES = {}  # name → (store, claim, expected status)
 META = {}   # name → {"trust", "filter", "scan", "parts", "dropped"}
 
 
+# The header / TxMeta ladder once more with EVERY header longer than the 8 KB the tipset prologue stages in LDS, so that every
+# slot of every route is answered by the prologue's general form (csrc/kernels/tipset_prepare_general.hip): each of these
+# cases has a twin `<name>_with_long_headers` with the SAME literal — a header's first field is IgnoredAny and decides nothing.
+LONG_HEADERS = "_with_long_headers"
+LONG_HEADER_BASES = frozenset("""
+    base_true parents_mismatch_order parents_mismatch_count child_epoch_mismatch parent_epoch_mismatch message_not_in_exec
+    missing_child_header missing_parent0_header missing_parent1_header missing_txmeta0 missing_txmeta1 missing_bls_root
+    missing_secp_root_of_the_last_parent undecodable_txmeta txmeta_as_a_3_tuple txmeta_as_a_1_tuple txmeta_root_null
+    txmeta_nonminimal_array_head_rehashes_differently txmeta_of_the_last_parent_rehashes_differently
+    two_missing_child_header_and_parents_mismatch two_wrong_child_epoch_and_missing_parent0
+    two_missing_parent0_and_parents_mismatch two_wrong_parent_epoch_and_missing_parent1 two_wrong_parent_epoch_and_missing_txmeta
+    two_txmeta0_mismatch_and_missing_parent1_header_is_the_header two_txmeta0_mismatch_and_missing_txmeta1
+    two_txmeta0_mismatch_and_missing_bls0 two_missing_secp0_and_txmeta1_mismatch two_txmeta_undecodable_and_mismatch_is_the_decode
+    child_header_15_tuple child_header_17_tuple parent0_header_15_tuple parent1_header_17_tuple child_parents_holds_a_byte_string
+    child_parents_is_not_an_array exec_duplicate_across_parents_first_position exec_first_parent_empty
+    undecodable_child_header undecodable_parent0_header undecodable_parent1_header
+    two_undecodable_child_header_and_wrong_child_epoch two_undecodable_parent0_and_wrong_parent_epoch""".split())
+# (the last five: their undecodable header is the one-byte BAD, which has no first field to lengthen — the OTHER headers are long)
+
+
+def long_field_0(make, n):
+    """header override: the case's own re-spelling `make` (or none) first, then field 0 of the tuple it wrote as a byte
+    string of n bytes; a block that is no such tuple stays as it is"""
+    def out(f):
+        b = make(f) if make else array(f)
+        return b[:1] + bstr(bytes(n)) + b[1 + len(f[0]):] if b[1:1 + len(f[0])] == f[0] else b
+    return out
+
+
 def case(name, expect, *, trust=None, filt=None, scan=None, **kw):
     """`scan`: {(filter, actor): expected triples} where the case has a scan answer written down"""
     assert name not in CASES, name
@@ -209,6 +238,11 @@ def case(name, expect, *, trust=None, filt=None, scan=None, **kw):
     st, claim, parts = tipset(salt=salt, **kw)
     CASES[name] = (st, claim, expect)
     META[name] = {"trust": trust, "filter": filt, "scan": scan, "parts": parts, "dropped": parts["dropped"]}
+    if name in LONG_HEADER_BASES:  # the twin, from the same keyword arguments
+        ch, ph = kw.get("child_header"), kw.get("parent_header")
+        case(name + LONG_HEADERS, expect, trust=trust, filt=filt, scan=scan,
+             **{**kw, "child_header": long_field_0(ch, 9000),
+                "parent_header": lambda k, f: long_field_0((lambda g: ph(k, g)) if ph else None, 9100 + 16 * k)(f)})
 
 
 def respell(i, new):
@@ -476,6 +510,13 @@ case("ignored_fields_hold_nested_arrays_and_maps", 1, child_header=lambda f: arr
 case("ignored_field_holds_an_undecodable_item", 66, child_header=respell(0, b"\xc1\x00"))
 # the tipset prologue stages 8 KB of a header; a longer one is legal (the first field is IgnoredAny)
 case("headers_longer_than_the_prologue_stage", 1, child_header=respell(0, bstr(bytes(9000))), parent_header=only(0, respell(0, bstr(bytes(9100)))))
+# … and a TxMeta beyond it: what is found under the TxMeta's CID is the pair and 9000 more bytes, so the decode fails at its
+# end (utils.rs:61) — in the LDS prologue the header fit and the TxMeta did not
+LONG_TXMETA = lambda f: array(f) + bytes(9000)  # noqa: E731
+case("txmeta0_with_a_trailer_longer_than_the_prologue_stage", 66, txmeta=only(0, LONG_TXMETA))
+case("txmeta1_with_a_trailer_longer_than_the_prologue_stage", 66, txmeta=only(1, LONG_TXMETA))
+# (headers come before any TxMeta: utils.rs:20-27)
+case("two_txmeta0_trailer_longer_than_the_prologue_stage_and_missing_parent1_header", 65, txmeta=only(0, LONG_TXMETA), drop=["parent1"])
 case("header_trailing_byte", 66, child_header=lambda f: array(f) + b"\x00")
 
 # ===== receipts ==================================================================================================================

@@ -70,7 +70,17 @@ def test_pyevents_gives_every_literal():
 def test_the_table_covers_what_it_must():
     seen = collections.Counter(ex for _, _, ex in ec.CASES.values())
     assert set(seen) == set(range(1, 18)) | {64, 65, 66, 67, 69, 71} == set(pyevents.STATUSES), seen
-    assert len(ec.CASES) >= 800 and len(ec.RC) >= 120
+    assert len(ec.CASES) >= 845 and len(ec.RC) >= 120
+    # the header / TxMeta ladder with every header beyond the prologue's 8 KB stage: same literal, and the headers ARE long
+    assert len(ec.LONG_HEADER_BASES) >= 42
+    for base in ec.LONG_HEADER_BASES:
+        st, _claim, expect = ec.CASES[base + ec.LONG_HEADERS]
+        parts = ec.META[base + ec.LONG_HEADERS]["parts"]
+        assert expect == ec.CASES[base][2], base
+        held = [len(st.blocks[c]) for c in [parts["child"]] + parts["parents"] if c in st.blocks]
+        assert all(n > 8192 or n < 16 for n in held) and sum(n > 8192 for n in held) >= len(held) - 1, (base, held)
+    assert sum(1 for n, (st, _c, ex) in ec.CASES.items() if "trailer_longer_than_the_prologue_stage" in n
+               and max(len(st.blocks.get(c, b"")) for c in ec.META[n]["parts"]["txmeta"]) > 8192 and ex in (65, 66)) == 3
     # every spelling of spelling_cases() is a receipt case, the good ones with the four perturbed claims beside the honest one
     for name, _ev, _em, bad in ec.spelling_cases():
         tags = {n.split(" / ")[1] for n in ec.CASES if n.startswith(f"spelling {name} / ") and n.count(" / ") == 1}
