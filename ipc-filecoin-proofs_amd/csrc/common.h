@@ -362,6 +362,17 @@ struct DevBuf {
         return hipMalloc(reinterpret_cast<void**>(&p), bytes);
     }
     size_t bytes() const { return count * sizeof(T); }
+    // hand the allocation over to a byte-typed buffer (a cache entry's): `to` owns it from here on, this one is empty
+    void move_to_bytes(DevBuf<uint8_t>& to) {
+        to.release();
+        to.p = reinterpret_cast<uint8_t*>(p);
+        to.count = count * sizeof(T);
+        to.cap = cap;
+        to.owner = owner;
+        p = nullptr;
+        count = cap = 0;
+        owner = nullptr;
+    }
     void swap(DevBuf& o) {
         std::swap(p, o.p);
         std::swap(count, o.count);
@@ -419,7 +430,7 @@ inline uint32_t div_up(uint64_t a, uint64_t b) { return uint32_t((a + b - 1) / b
 }  // namespace ipcfp
 
 namespace ipcfp {
-// A cached `Amt::for_each` enumeration of one AMT of the witness (amt_enum.hip): the leaf values in
+// A cached `Amt::for_each` enumeration of one AMT of the witness (host/amt_enumerate.cpp): the leaf values in
 // index order.  Valid until the witness index is rebuilt.
 struct EnumCached {
     uint64_t root[5];
@@ -485,3 +496,11 @@ struct ipcfp_witness {
     bool bt_has_filter = false;
     ipcfp::ScanParams bt_filter{};  // the filter whose matches BlockRec::kind_matches counts
 };
+
+namespace ipcfp {
+// the CID → block-id index of the witness's current tables (kernels/cid_index.hip)
+int witness_build_index(ipcfp_ctx* ctx, ipcfp_witness* w);
+// the common tail of every way a witness comes into being: device tables from raw bytes + offsets (host/witness.cpp)
+int witness_finish_create(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* raw_bytes_d, const uint64_t* raw_off_d,
+                          const uint32_t* len_d_src, const uint8_t* cids_d_src);
+}  // namespace ipcfp

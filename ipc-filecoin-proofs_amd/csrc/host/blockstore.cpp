@@ -22,11 +22,6 @@
 
 using namespace ipcfp;
 
-namespace ipcfp {
-int witness_finish_create(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* raw_bytes_d, const uint64_t* raw_off_d,
-                          const uint32_t* len_d_src, const uint8_t* cids_d_src);
-}
-
 extern "C" {
 
 int ipcfp_witness_has(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* cids40, uint64_t n, uint8_t* has,

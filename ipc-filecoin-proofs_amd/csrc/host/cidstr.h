@@ -23,4 +23,12 @@ void blake2b256_host(const uint8_t* data, size_t len, uint8_t out32[32]);
 // hex digits → bytes; false on odd length / non-hex
 bool hex_decode(const char* s, size_t n, std::vector<uint8_t>& out);
 
+struct CidKey;  // kernels/witness_dev.h: a 40-byte slot as the device compares it
+// an ABI slot as a witness key (host/primitives.cpp)
+CidKey key_from_slot(const uint8_t* slot40);
+// Parse a CID string into a witness key (host/verify_storage.cpp).  `parsed`: Cid::try_from succeeded.  `canonical`: the
+// string equals Cid::to_string() of what it parses to.  A CID longer than the 40-byte slot becomes its fold
+// (cid_to_slot), the key the device makes of the same CID when it reads it out of a block.
+void parse_cid_claim(const char* s, CidKey& key, bool& parsed, bool& canonical);
+
 }  // namespace ipcfp

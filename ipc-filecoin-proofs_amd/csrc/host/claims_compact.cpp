@@ -17,10 +17,6 @@
 
 namespace ipcfp {
 
-int verify_packed(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& tcs, const EventClaimPacked* claims_d, uint32_t n,
-                  const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust, const ipcfp_event_filter_t* filter,
-                  uint8_t* status_d, void* where_d = nullptr, ScanRide* ride = nullptr);
-
 int claims_ready(ipcfp_ctx* ctx) {
     int rc = upload_task_wait(ctx);
     if (ctx->claims_rebase.pending) {  // a slice of a larger batch: its blob offsets become offsets into what was uploaded

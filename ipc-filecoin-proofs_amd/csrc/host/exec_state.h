@@ -8,6 +8,7 @@
 #include "../kernels/tipset_ctx.h"
 #include "../kernels/types_dev.h"
 #include "../kernels/launch.h"
+#include "cidstr.h"
 
 namespace ipcfp {
 
@@ -27,6 +28,12 @@ struct ExecState {
     uint64_t raw_len = 0, exec_len = 0;
     uint32_t status = IPCFP_ST_ERR;
 };
+// slots of the execution order's hash table for n raw positions: a power of two, load ≤ 0.5 (ExecState::mask = size - 1)
+inline uint32_t exec_table_size(uint32_t n) {
+    uint32_t size = 64;
+    while (size < 2ull * n) size <<= 1;
+    return size;
+}
 
 // reconstruct_execution_order (verify_txmeta = 1, events/utils.rs:16-30) or build_execution_order
 // (verify_txmeta = 0, events/utils.rs:32-46) of the context stored at ctx_d (device).  With a recording
@@ -76,6 +83,16 @@ struct ScanRide {
     uint32_t status = IPCFP_ST_ERR;
     uint64_t n_idx = 0, n_matches = 0;
 };
+// Shared device path of the string and the packed entry points (verify_events.cpp): prepare every tipset context (header
+// facts, execution order) and verify the batch.  `claims_d`, `blob_d`, `status_d` are device.
+int verify_packed(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& tcs, const EventClaimPacked* claims_d,
+                  uint32_t n, const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust,
+                  const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d = nullptr, ScanRide* ride = nullptr);
+// `verify_event_proof` for a batch of ONE tipset pair without a mid-call synchronisation (verify_fast.cpp).  *done = false
+// on return: not that route's case, or its dense walk did not hold — verify_packed (verify_events.cpp) does the batch.
+int verify_packed_fast(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& tcs, const EventClaimPacked* claims_d,
+                       uint32_t n, const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust,
+                       const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d, bool* done, ScanRide* ride);
 ScanParams scan_params_of(const ipcfp_event_filter_t& filter, int has_actor, uint64_t actor);
 // the look-back state of k_scan_tail_fused for n_tiles tiles (context-owned; zeroed when (re)allocated)
 int scan_tail_scratch(ipcfp_ctx* ctx, uint32_t n_tiles, unsigned long long** out);
@@ -101,7 +118,5 @@ const uint32_t* event_table_counts(const EventTableCached* t, const ipcfp_event_
 
 // queue the block-order event parse of the witness on the aux stream unless its block table exists (scan_events.cpp)
 int block_table_prefetch(ipcfp_ctx* ctx, ipcfp_witness* w, const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor);
-
-CidKey key_from_slot(const uint8_t* slot40);
 
 }  // namespace ipcfp

@@ -19,8 +19,6 @@
 
 namespace ipcfp {
 
-void parse_cid_claim(const char* s, CidKey& key, bool& parsed, bool& canonical);
-
 namespace {
 
 bool parse_hex0x(const char* s, std::vector<uint8_t>& out) {

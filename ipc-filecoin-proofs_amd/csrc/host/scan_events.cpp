@@ -14,10 +14,6 @@
 using namespace ipcfp;
 
 namespace ipcfp {
-CidKey key_from_slot(const uint8_t* slot40);
-}
-
-namespace ipcfp {
 
 // The host's side of the mailbox (common.h): spin until the device has published sequence number `seq`.  A launch that
 // failed never publishes: after 5 s the stream is drained, which surfaces the error.

@@ -28,11 +28,6 @@
 
 using namespace ipcfp;
 
-namespace ipcfp {
-int witness_finish_create(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* raw_bytes_d, const uint64_t* raw_off_d,
-                          const uint32_t* len_d_src, const uint8_t* cids_d_src);
-}
-
 // ---- RCCL, resolved at run time ------------------------------------------------------------------------------
 namespace {
 

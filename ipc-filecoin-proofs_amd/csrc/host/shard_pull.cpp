@@ -18,14 +18,9 @@
 #include "../common.h"
 #include "../kernels/launch.h"
 #include "../kernels/shard_pull.h"
+#include "cidstr.h"
 
 using namespace ipcfp;
-
-namespace ipcfp {
-int witness_finish_create(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* raw_bytes_d, const uint64_t* raw_off_d,
-                          const uint32_t* len_d_src, const uint8_t* cids_d_src);
-CidKey key_from_slot(const uint8_t* slot40);
-}  // namespace ipcfp
 
 extern "C" {
 

@@ -12,10 +12,9 @@
 
 #include "../common.h"
 #include "../kernels/tipset_ctx.h"
+#include "cidstr.h"
 
 namespace ipcfp {
-
-CidKey key_from_slot(const uint8_t* slot40);
 
 // the device copies of the wide keys of one call (alive until the call's entry point returns)
 struct WideParents {

@@ -27,9 +27,6 @@ using namespace ipcfp;
 
 namespace ipcfp {
 
-void parse_cid_claim(const char* s, CidKey& key, bool& parsed, bool& canonical);
-CidKey key_from_slot(const uint8_t* slot40);
-
 int exec_state_prepare(ipcfp_ctx* ctx, ExecState& ex, uint32_t n_parents) {
     IPCFP_HIP(ctx, ex.roots.alloc(2 * size_t(n_parents) + 1));
     IPCFP_HIP(ctx, ctl_words(ctx, ex.err_own, ex.err.p, 1, true));  // kNoEnumError
@@ -61,8 +58,7 @@ int build_exec_order(ipcfp_ctx* ctx, const WitnessView& view, const TipsetCtxDev
     if (ex.status != IPCFP_ST_TRUE) return IPCFP_OK;
     const uint32_t n = uint32_t(en.n_leaves);
     ex.raw_len = n;
-    uint32_t size = 64;
-    while (size < 2ull * n) size <<= 1;
+    const uint32_t size = exec_table_size(n);
     ex.mask = size - 1;
     if (!en.keys_written) IPCFP_HIP(ctx, ex.keys.alloc(n));
     IPCFP_HIP(ctx, ex.slots.alloc(size));
@@ -88,13 +84,9 @@ int build_exec_order(ipcfp_ctx* ctx, const WitnessView& view, const TipsetCtxDev
 
 // Shared device path of the string and the packed entry points: prepare every tipset context
 // (header facts, execution order) and verify the batch.  `claims_d`, `blob_d`, `status_d` are device.
-int verify_packed_fast(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& tcs, const EventClaimPacked* claims_d,
-                       uint32_t n, const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust,
-                       const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d, bool* done, ScanRide* ride);  // verify_fast.cpp
-
 int verify_packed(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDev>& tcs, const EventClaimPacked* claims_d,
                   uint32_t n, const uint8_t* blob_d, uint64_t blob_len, const ipcfp_trust_policy_t* trust,
-                  const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d = nullptr, ScanRide* ride = nullptr) {
+                  const ipcfp_event_filter_t* filter, uint8_t* status_d, void* where_d, ScanRide* ride) {
     static const ipcfp_trust_policy_t accept_all = {0, 0, 0, 0};
     {   // one tipset pair, receipts not enumerated yet: the route without a mid-call synchronisation (verify_fast.cpp);
         // whenever its dense walk does not hold, everything is done again below

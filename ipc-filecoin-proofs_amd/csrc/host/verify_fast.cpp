@@ -32,8 +32,6 @@ using namespace ipcfp;
 
 namespace ipcfp {
 
-int exec_state_prepare(ipcfp_ctx* ctx, ExecState& ex, uint32_t n_parents);
-
 // → IPCFP_OK with *done = true: status_d (and where_d) hold the batch's results;
 //   IPCFP_OK with *done = false: not this route's case, or the dense walk did not hold — nothing the caller may use;
 //   anything else: an ABI error.
@@ -101,7 +99,9 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     DevBuf<DenseNode> dense_frontier;
     DevBuf<uint32_t> small_own;
     DevBuf<uint64_t> info_own;
-    uint32_t* small = nullptr;  // [0] = max height (unused here), [2] = anomaly flag (the dense walk)
+    // [2] = anomaly flag (the dense walk).  Four words although one is used: every control word taken behind these keeps the
+    // offset it has always had in the step's control block.
+    uint32_t* small = nullptr;
     uint64_t* info_d = nullptr;
     IPCFP_HIP(ctx, frontier.alloc(n_all));
     IPCFP_HIP(ctx, dense_frontier.alloc(n_all));
@@ -116,8 +116,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     if (rc) return rc;
     // ---- the roots; their shapes come back through the mailbox ----
     const unsigned long long seq = ++ctx->mailbox_seq;
-    rc = launch_enum_roots(ctx, view, ex.roots.p, n_all, VK_CID, frontier.p, small, ex.err.p, info_d, ctx->mailbox_dev, seq,
-                           dense_frontier.p);
+    rc = launch_enum_roots(ctx, view, ex.roots.p, n_all, VK_CID, frontier.p, ex.err.p, info_d, ctx->mailbox_dev, seq, dense_frontier.p);
     if (rc) return rc;
     prof.reset();
     {
@@ -148,8 +147,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
     IPCFP_HIP(ctx, ex.keys.alloc(n_msgs));
     IPCFP_HIP(ctx, rleaves.alloc(n_rcpt));
     // the execution order's hash table and first-occurrence flags: sized now, cleared by the walk's last kernel on the way
-    uint32_t size = 64;
-    while (size < 2ull * n_msgs) size <<= 1;
+    const uint32_t size = exec_table_size(n_msgs);
     ex.mask = size - 1;
     ex.raw_len = n_msgs;
     IPCFP_HIP(ctx, ex.slots.alloc(size));
@@ -298,13 +296,7 @@ static int verify_packed_fast_queue(ipcfp_ctx* ctx, ipcfp_witness* w, std::vecto
         en->n = n_rcpt;
         en->error = kNoEnumError;
         en->dense = true;
-        en->leaves.p = reinterpret_cast<uint8_t*>(rleaves.p);
-        en->leaves.count = rleaves.count * sizeof(LeafRef);
-        en->leaves.cap = rleaves.cap;
-        en->leaves.owner = rleaves.owner;
-        rleaves.p = nullptr;
-        rleaves.count = rleaves.cap = 0;
-        rleaves.owner = nullptr;
+        rleaves.move_to_bytes(en->leaves);
         w->enum_cache.push_back(std::move(en));
         std::memcpy(table->root, facts.receipts_root.w, 40);
         w->table_cache.push_back(std::move(table));

@@ -17,11 +17,6 @@ using namespace ipcfp;
 
 namespace ipcfp {
 
-CidKey key_from_slot(const uint8_t* slot40);
-
-// Parse a CID string into a witness key.  `parsed`: Cid::try_from succeeded.  `canonical`: the
-// string equals Cid::to_string() of what it parses to.  A CID longer than the 40-byte slot becomes its fold
-// (cidstr.h cid_to_slot), the key the device makes of the same CID when it reads it out of a block.
 void parse_cid_claim(const char* s, CidKey& key, bool& parsed, bool& canonical) {
     std::vector<uint8_t> bin;
     parsed = cid_from_string(s, bin);

@@ -21,10 +21,6 @@
 using namespace ipcfp;
 
 namespace ipcfp {
-int witness_build_index(ipcfp_ctx* ctx, ipcfp_witness* w);  // cid_index.hip
-}
-
-namespace ipcfp {
 
 constexpr uint64_t kTailSlack = 256;  // K1 may read one 128-byte chunk past a block's padded end
 

@@ -13,17 +13,21 @@
 // recorded as (sequence number, base index of the failing node, status code) packed into one u64
 // and combined with atomicMin — the minimum IS the first failure in depth-first order, because a
 // failing node has no descendants and every node with a smaller base index is visited earlier.
+//
+// Where what lives:
+//   amt_dense_plan.h         the dense walk's plan (host arithmetic that sizes every buffer; compiles without HIP)
+//   amt_dense_dev.h          the canonical spelling of a dense node, for the two units below
+//   amt_dense.hip            the dense walk: its kernels and launch_dense_walk
+//   amt_enum.hip             k_enum_roots, the general walk's kernels, k_check_dense, and their launchers
+//   host/amt_enumerate.cpp   amt_enumerate and the witness's enumeration cache: host code over the launchers
 #pragma once
 #include <cstdint>
 #include <vector>
 
 #include "../common.h"
+#include "amt_dense_plan.h"
 #include "amt_types.h"
 #include "walk_dev.h"
-
-namespace ipcfp {
-
-}  // namespace ipcfp
 
 struct ipcfp_ctx;
 struct ipcfp_witness;
@@ -35,7 +39,7 @@ struct AmtEnumResult {
     DevBuf<LeafRef> leaves;
     uint64_t n_leaves = 0;
     uint64_t error = kNoEnumError;  // packed first error (after the final sync)
-    bool dense = false;             // every AMT held exactly the indices 0..count-1 (the fast path succeeded)
+    bool dense = false;             // every AMT held exactly the indices 0..count-1 (the dense walk succeeded)
     bool keys_written = false;      // the values (links) went to the caller's key buffer instead of `leaves`
 };
 
@@ -43,9 +47,9 @@ struct AmtEnumResult {
 // subtrees that hold no index of the range are neither resolved nor loaded — their blocks live in another
 // shard's witness — while every node that is visited is validated completely.  Meant for ONE root.
 
-// One more AMT riding along with a call (dense fast path only): its spec is roots_d[n_roots], written by the caller
+// One more AMT riding along with a call (dense walk only): its spec is roots_d[n_roots], written by the caller
 // or by a kernel queued before; its values have their own type and index range and go to a result of their own.
-// `done` stays false when the fast path did not take it (not dense, failed to load, anomaly): the caller then
+// `done` stays false when the dense walk did not take it (not dense, failed to load, anomaly): the caller then
 // enumerates it by itself.  This is how the verify path walks the receipts AMT in the same launches as the
 // message AMTs of the execution order instead of in a second chain of per-level launches.
 struct EnumExtra {
@@ -55,31 +59,7 @@ struct EnumExtra {
     bool done = false;
 };
 
-// ---- the dense fast path (amt_enum.hip): the tree's shape follows from the roots' (height, bit width, count) ----
-struct DenseRoot {
-    uint32_t height, bit_width;
-    uint64_t count;
-    uint64_t lo, hi;  // the indices to enumerate: [lo, hi) with lo < hi <= count, or (0, 0) for an empty tree
-    uint32_t vkind;   // value type of this tree
-    uint32_t out_sel; // where its values go: 0 = keys_out (links as witness keys), 1 = leaves, 2 = leaves of the extra root
-    uint64_t out_off; // ... from this element on
-};
-constexpr uint32_t kMaxDenseRoots = 2 * IPCFP_MAX_PARENTS + 1;  // BLS + secp per parent block, + the receipts AMT
-constexpr uint32_t kMaxDenseLevels = 24;
-// interior levels of at most this many entries at the top of the walk share ONE single-workgroup launch (k_dense_top)
-constexpr uint32_t kDenseTopMax = 1024;
-struct DenseRoots {  // travels as a kernel ARGUMENT (1.6 KB): no copy at the head of the walk
-    DenseRoot r[kMaxDenseRoots];
-    uint32_t n;
-};
-struct DensePlan {
-    bool ok = false;          // every root is a dense candidate: the walk below may be launched
-    uint32_t n_use = 0;       // roots in the walk (the call's own + the extra one when it joined)
-    uint32_t max_height = 0;
-    uint64_t n_level[kMaxDenseLevels] = {};  // nodes per level (node height)
-    uint64_t n_leaves = 0, n_extra = 0, biggest = 0;
-    DenseRoots roots{};
-};
+// ---- the dense walk (amt_dense.hip; plan: amt_dense_plan.h) ----
 // what k_dense_link_leaves clears on the side (launch_dense_walk `clear`; only when the plan has key values)
 struct DenseClear {
     unsigned long long* slots;  // n_slots × ~0
@@ -97,8 +77,6 @@ struct DenseReceiptOut {
     uint32_t* counts;          // nullable: matches of the table's filter (kWalkPending where the table does not cover)
     unsigned long long* err;   // the missing events blocks' error word (set to kNoEnumError by the walk's first interior launch)
 };
-void dense_plan(const std::vector<uint64_t>& root_info, uint32_t n_roots, int vkind, bool want_keys, uint64_t lo, uint64_t hi,
-                uint32_t has_extra, int extra_vkind, uint64_t extra_lo, uint64_t extra_hi, DensePlan& plan);
 int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* frontier, const DensePlan& plan,
                       DenseNode* a, DenseNode* b, LeafRef* leaves_main, CidKey* keys_main, LeafRef* leaves_extra, uint32_t* anomaly_d,
                       hipStream_t leaves_stream = nullptr,  // non-null (with fork_event): k_dense_leaves runs there, beside
@@ -107,19 +85,36 @@ int launch_dense_walk(ipcfp_ctx* ctx, const WitnessView& view, const DenseNode* 
                       // non-null: the extra root's leaves take k_dense_receipt_leaves (a receipts tree), on the leaves' stream
                       const DenseReceiptOut* receipts = nullptr);
 
+// ---- amt_enum.hip: every launcher enqueues on ctx->stream and returns without synchronising ----
+// The roots → their frontier entries (general and dense form) and their shapes root_info_d[2t] = {height | bw << 32, count}
+// (~0: the root did not load).  `mailbox` (pinned host, nullable): the shapes also go there, for a caller that queues the
+// walk itself without draining the stream (host/verify_fast.cpp).  The launch shape follows from it:
+//   mailbox == nullptr   div_up(n_all, 64) workgroups of 64 lanes, any number of roots (amt_enumerate);
+//   mailbox != nullptr   ONE workgroup of 64 lanes, or of 128 when n_all > 64 — the kernel publishes the sequence number
+//                        behind a __syncthreads, so every root must sit in that workgroup: at most 128 roots, else an error.
 int launch_enum_roots(ipcfp_ctx* ctx, const WitnessView& view, const AmtRootSpec* roots_d, uint32_t n_all, int vkind,
-                      EnumNode* frontier_d, uint32_t* max_height_d, unsigned long long* err_d, uint64_t* root_info_d,
-                      unsigned long long* mailbox, unsigned long long mailbox_seq, DenseNode* dense_frontier_d);
-struct TipsetCtxDev;
-int launch_txmeta_rehash(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& view, const TipsetCtxDev* ctx_d, unsigned long long* err_d);
+                      EnumNode* frontier_d, unsigned long long* err_d, uint64_t* root_info_d, unsigned long long* mailbox,
+                      unsigned long long mailbox_seq, DenseNode* dense_frontier_d);
+// one level of the general walk.  counts_d[t]: entries frontier entry t gives the next level (level ≥ 1), or its values
+// inside [lo, hi) (level 0) — then launch_scan_u32, and launch_enum_expand / launch_enum_emit place them
+int launch_enum_count(ipcfp_ctx* ctx, const WitnessView& view, const EnumNode* frontier_d, uint32_t n, uint32_t level, int vkind,
+                      uint32_t* counts_d, unsigned long long* err_d, uint64_t lo, uint64_t hi);
+int launch_enum_expand(ipcfp_ctx* ctx, const WitnessView& view, const EnumNode* frontier_d, uint32_t n, uint32_t level,
+                       const uint32_t* offsets_d, uint32_t total, EnumNode* next_d, unsigned long long* err_d, uint64_t lo, uint64_t hi);
+int launch_enum_emit(ipcfp_ctx* ctx, const WitnessView& view, const EnumNode* frontier_d, uint32_t n, int vkind,
+                     const uint32_t* counts_d, const uint32_t* offsets_d, LeafRef* leaves_d, uint64_t lo, uint64_t hi);
+// *flag_d |= 1 unless leaves_d[i].index == first + i for every i
+int launch_check_dense(ipcfp_ctx* ctx, const LeafRef* leaves_d, uint32_t n, uint64_t first, uint32_t* flag_d);
 
+// ---- host/amt_enumerate.cpp ----
 // Enumerate `n_roots` AMTs (device array `roots_d`) whose values have type `vkind`.
 // `err_d` is a device u64 initialised by the caller (kNoEnumError or earlier-stage errors); the
-// enumerator atomicMin's into it.  Synchronises the stream twice on the dense path (root shapes; anomaly flag
-// + error word), once more per level on the general path.
+// enumerator atomicMin's into it.  Three steps: the roots (one synchronisation: their shapes); the dense walk when the
+// plan allows it (one more: anomaly flag + error word); otherwise — or after an anomaly — the general walk, level by
+// level (one per level, and one for the error word).
 int amt_enumerate(ipcfp_ctx* ctx, const WitnessView& view, const AmtRootSpec* roots_d, uint32_t n_roots, int vkind,
                   unsigned long long* err_d, AmtEnumResult& out, uint64_t lo = 0, uint64_t hi = ~0ULL,
-                  DevBuf<CidKey>* keys_out = nullptr,  // VK_CID on the dense path: the links as witness keys, no LeafRefs
+                  DevBuf<CidKey>* keys_out = nullptr,  // VK_CID on the dense walk: the links as witness keys, no LeafRefs
                   EnumExtra* extra = nullptr);
 
 // hand a finished enumeration of one AMT to the witness's cache (what amt_enumerate_cached would have produced)

@@ -29,7 +29,7 @@ struct EnumNode {
     uint8_t leaf_ready; // a Leaf node met above height 0: carried down unchanged
 };
 
-// one frontier entry of the DENSE walk (amt_enum.hip): where the node's bytes lie, so that the level below starts
+// one frontier entry of the DENSE walk (amt_dense.hip): where the node's bytes lie, so that the level below starts
 // reading them without first asking the off / len tables
 struct DenseNode {
     uint64_t goff;    // arena offset of the node's first byte

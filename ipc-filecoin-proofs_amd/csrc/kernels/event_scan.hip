@@ -7,7 +7,7 @@
 //   PASS 2 (:242-301)  for matching receipts only: r_amt.get(i) (records the receipt path), the events
 //                      AMT walked again on a recorder, one EventProof per matching event in index order.
 // The receipt list the reference takes from RPC (:199-204) is the receipts AMT enumerated in index
-// order (amt_enum.hip).  K8: with `touched` set in the WitnessView, PASS 2 marks exactly the blocks
+// order (host/amt_enumerate.cpp).  K8: with `touched` set in the WitnessView, PASS 2 marks exactly the blocks
 // the reference's RecordingBlockStores see (rec_receipts + one rec_events per matching receipt,
 // src/proofs/common/blockstore.rs:26-30); PASS 1 runs untracked, like the throw-away recorder.
 #include <hip/hip_runtime.h>

@@ -61,7 +61,7 @@ constexpr uint64_t kEvIsLog = 1ull << 56, kEvCaseA = 1ull << 57;
 //     (or is no events AMT at all) is RK_WALK, which decides nothing.
 //   k_receipt_events (event_scan.hip)  one receipt per lane: events_root → block id → BlockRec → ReceiptRec.  On the
 //     verify call's table route the receipts tree's leaf kernel writes the same records while it holds each receipt
-//     (k_dense_receipt_leaves, amt_enum.hip).  Receipts whose block is RK_WALK take the general walkers (k_receipt_walk).
+//     (k_dense_receipt_leaves, amt_dense.hip).  Receipts whose block is RK_WALK take the general walkers (k_receipt_walk).
 struct BlockRec {
     uint32_t kind_matches;  // bits 0..7: RK_TABLE | RK_WALK; bits 8..31: events matching the filter the table was built with
     uint32_t first;         // index of the first EventRec

@@ -153,6 +153,9 @@ int launch_tipset_prepare(ipcfp_ctx* ctx, const WitnessView& w, const void* jobs
                           const void* inline_inputs = nullptr);  // host TipsetInputs of the one context: sent as a kernel argument
 int launch_exec_roots(ipcfp_ctx* ctx, const WitnessView& w, const TipsetCtxDev* ctx_d, AmtRootSpec* roots_d,
                       unsigned long long* err_d, int verify_txmeta = 1, uint32_t n_parents = 0);
+// the prologue's deferred half: the TxMeta re-hashes launch_tipset_prepare(defer_rehash) left behind (tipset_ctx.h
+// txmeta_block), on `stream`
+int launch_txmeta_rehash(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& view, const TipsetCtxDev* ctx_d, unsigned long long* err_d);
 // the whole prologue of ONE context with a tipset key wider than the inline form (job: host PrepareJob)
 int launch_tipset_prepare_wide(ipcfp_ctx* ctx, const WitnessView& w, const void* job, uint32_t n_parents);
 int launch_exec_dedup(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* leaves_d, uint32_t n, CidKey* keys_d,

@@ -1,6 +1,6 @@
 // csrc/kernels/scan.hip — device-wide exclusive prefix sum of u32 counts (three small kernels:
 // tile sums, scan of tile sums, apply).  Used wherever a level of a tree walk places its children
-// or matches in index order (amt_enum.hip, event_scan.hip, exec-order dedup).
+// or matches in index order (the general AMT walk: amt_enum.hip / host/amt_enumerate.cpp; event_scan.hip; exec-order dedup).
 #include <hip/hip_runtime.h>
 
 #include "../common.h"

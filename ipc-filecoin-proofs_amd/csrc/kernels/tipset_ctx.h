@@ -37,7 +37,7 @@ struct TipsetCtxDev {
     uint32_t pad0;
     unsigned long long prologue_general;  // bit s: slot s of the tipset prologue is left to the general kernel (a block larger than the LDS stage)
     long long parent0_height;
-    // 1 + the TxMeta block of parent b when its re-hash was LEFT to k_txmeta_rehash (amt_enum.hip; tipset_prologue_body.h
+    // 1 + the TxMeta block of parent b when its re-hash was LEFT to k_txmeta_rehash (tipset_prepare_general.hip; tipset_prologue_body.h
     // prologue_roots with kTxMetaDefer); 0: nothing to re-hash (checked inline, or never reached) — so that a context
     // taken from zeroed memory needs no initialisation.
     uint32_t txmeta_block[IPCFP_MAX_PARENTS];
@@ -54,7 +54,7 @@ struct TipsetCtxDev {
     const uint32_t* exec_pos;     // raw position → execution index (valid where the position is a first occurrence)
     const uint32_t* exec_inv;     // execution index → raw position of that message's first occurrence (k_exec_finish)
     uint64_t exec_len;            // number of distinct messages
-    // receipts AMT enumerated once per context (amt_enum.hip): when it decoded without error and is
+    // receipts AMT enumerated once per context (host/amt_enumerate.cpp): when it decoded without error and is
     // dense, `Amt::get(exec_index)` is a table lookup — every node on every path was already validated
     const LeafRef* receipt_leaves;
     uint64_t n_receipt_leaves;

@@ -1,8 +1,9 @@
 // csrc/kernels/tipset_prepare_general.hip — the tipset prologue (tipset_prologue_body.h) with the general, global-memory
 // reader: the one-context form of the generator / shard-plan paths and of wide tipset keys (k_tipset_prepare_one), and
 // the companion of the LDS prologue (tipset_prepare.hip) for the slots whose blocks do not fit its stage
-// (k_tipset_prepare_flagged).  A unit of its own so that these single-wavefront workgroups carry 8 KB of LDS and not
-// the line-staging area of verify_events.hip: beside the block-order event parse a 43 KB workgroup waits for a CU to drain.
+// (k_tipset_prepare_flagged); and the prologue's deferred half, the TxMeta re-hashes (k_txmeta_rehash).  A unit of its
+// own so that these single-wavefront workgroups carry 8 KB of LDS and not the line-staging area of verify_events.hip:
+// beside the block-order event parse a 43 KB workgroup waits for a CU to drain.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -86,6 +87,59 @@ int launch_exec_roots(ipcfp_ctx* ctx, const WitnessView& w, const TipsetCtxDev* 
     return launch_prepare_one(ctx, w, PrepareJob{const_cast<TipsetCtxDev*>(ctx_d), roots_d, err_d}, 2,
                               n_parents > IPCFP_MAX_PARENTS ? n_parents : IPCFP_MAX_PARENTS,
                               verify_txmeta ? kTxMetaCheck : kTxMetaNone);  // 0: the generator (build_execution_order, utils.rs:44)
+}
+
+// The prologue's deferred half — the TxMeta re-hash of parent block b, left behind by the LDS prologue in kTxMetaDefer
+// mode (tipset_ctx.h txmeta_block): put_cbor(&(bls_root, secp_root), Blake2b256) must give the CID the header named
+// (src/proofs/events/utils.rs:65-72; the verify path always checks).  The block was decoded by the prologue already; its
+// CID is the key it was found under.
+__device__ __forceinline__ void txmeta_rehash_lane(const WitnessView& w, const TipsetCtxDev& c, uint32_t b, unsigned long long* __restrict__ err) {
+    if (b >= c.n_parents || b >= IPCFP_MAX_PARENTS) return;
+    if (c.txmeta_block[b] == 0u) return;  // (1 + block id: tipset_ctx.h)
+    const uint32_t tb = c.txmeta_block[b] - 1u;
+    const uint32_t seq = c.n_parents + 3 * b;
+    auto fail = [&](uint32_t code) { atomicMin(err, (unsigned long long)pack_enum_error(seq, 0, code)); };
+    Rd r;
+    r.init(w.arena + w.off[tb], w.len[tb]);
+    uint32_t o[2], l[2];
+    if (!txmeta_links(r, o[0], l[0], o[1], l[1]) || l[0] > 64u || l[1] > 64u) {  // (the prologue took this very block: not reachable)
+        fail(IPCFP_ST_ERR_DECODE);
+        return;
+    }
+    CidKey re;
+    if (w.len[tb] == 87u && o[0] == 6u && l[0] == 38u && o[1] == 49u && l[1] == 38u) {
+        // `82 | d8 2a 58 27 00 ‖ 38 | d8 2a 58 27 00 ‖ 38`: the canonical re-encoding IS the block — one compression
+        // straight from its bytes (blocks sit on 128-byte lines with tail slack), no byte buffer in scratch
+        uint64_t m[16];
+        const ulonglong2* q = reinterpret_cast<const ulonglong2*>(w.arena + w.off[tb]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const ulonglong2 v = k < 6 ? q[k] : ulonglong2{0ull, 0ull};
+            m[2 * k] = v.x;
+            m[2 * k + 1] = v.y;
+        }
+        b2b::mask_tail(m, 87u);
+        uint64_t h[8];
+        b2b::init256(h);
+        b2b::compress(h, m, 87ull, true);
+        txmeta_cid_of_digest(h, re);
+    } else {
+        txmeta_rehash(r, o[0], l[0], o[1], l[1], re);
+    }
+    if (!cid_equal(re, load_cid_slot(w.cids, tb))) fail(IPCFP_ST_ERR_TXMETA_MISMATCH);
+}
+
+// one lane per parent block.  Nothing waits for this launch but the end of the call (host/verify_fast.cpp queues it on
+// the aux stream behind the receipts' event records): as a second workgroup of k_enum_roots it took 123 µs and held
+// the first level of the walk back for as long.
+__global__ __launch_bounds__(64) void k_txmeta_rehash(WitnessView w, const TipsetCtxDev* __restrict__ c, unsigned long long* __restrict__ err) {
+    txmeta_rehash_lane(w, *c, threadIdx.x, err);
+}
+
+int launch_txmeta_rehash(ipcfp_ctx* ctx, hipStream_t stream, const WitnessView& view, const TipsetCtxDev* ctx_d, unsigned long long* err_d) {
+    hipLaunchKernelGGL(k_txmeta_rehash, dim3(1), dim3(64), 0, stream, view, ctx_d, err_d);
+    IPCFP_HIP(ctx, hipGetLastError());
+    return IPCFP_OK;
 }
 
 void launch_tipset_prepare_lds(hipStream_t stream, const WitnessView& w, const PrepareJobs& jobs, uint32_t n_jobs, bool defer_rehash,

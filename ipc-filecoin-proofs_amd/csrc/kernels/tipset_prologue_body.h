@@ -27,7 +27,7 @@ namespace ipcfp {
 // put_cbor(&(bls_root, secp_root), Blake2b256) must give the CID the header named (utils.rs:65-72) …
 enum TxMetaMode : int {
     kTxMetaCheck = 0,  // … checked here, on the lead lane (reconstruct_execution_order: the verify path always checks)
-    kTxMetaDefer = 1,  // … left to k_txmeta_rehash (amt_enum.hip): txmeta_block[b] = block + 1 (tipset_ctx.h); inline keys only
+    kTxMetaDefer = 1,  // … left to k_txmeta_rehash (tipset_prepare_general.hip): txmeta_block[b] = block + 1 (tipset_ctx.h); inline keys only
     kTxMetaNone = 2,   // … never compared: the generator's build_execution_order (utils.rs:44)
 };
 

@@ -1,4 +1,4 @@
-"""GPU: AMT enumeration on shapes that leave the dense fast path (amt_enum.hip): sparse indices, a lying
+"""GPU: AMT enumeration on shapes that leave the dense walk (amt_dense.hip): sparse indices, a lying
 `count`, a non-minimal height, an empty tree — the scan must fall back to the general level-synchronous
 walk and still agree with the oracle bit for bit."""
 import numpy as np
@@ -41,7 +41,7 @@ CASES = {
     "count too small": dict(idx=range(50), count=40),
     "count zero but values": dict(idx=range(5), count=0),
     "tall root": dict(idx=range(20), height=3),
-    # dense, but one interior link is a 36-byte sha2-256 CID: the 43-byte link stride of the fast path is wrong
+    # dense, but one interior link is a 36-byte sha2-256 CID: the 43-byte link stride of the dense walk is wrong
     "odd link first child": dict(idx=range(600), odd_links={(1, 0)}),
     "odd link middle": dict(idx=range(600), odd_links={(0, 264), (1, 128)}),
     "odd link last": dict(idx=range(600), odd_links={(0, 592)}),
