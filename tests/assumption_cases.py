@@ -135,6 +135,121 @@ STORAGE_CASES = {
 }
 
 
+# --- the same assumptions as the GET PRIMITIVES meet them (tests/hamt_get_cases.py) -----------------------------------------
+# Each case: name → callable(value kind) → (store, root CID, bit width, [(key, expected status, value bytes | None)], the
+# limit it stands at | None), or None where the kind has no such case.  tests/hamt_get_cases.py takes them into its table:
+# tests/test_hamt_get_cases.py holds pystorage and the oracle to them, tests/test_gpu_hamt_get_cases.py every route.
+def _hg():
+    import hamt_get_cases as hg
+
+    return hg
+
+
+def _get_case(node_of, probes_of, bw=5, limit=None):
+    """node_of(hg, kind) → the root node's bytes; probes_of(hg, kind) → [(key, status, value)]"""
+    def make(kind):
+        hg = _hg()
+        st = pyamt.Store()
+        return st, st.put(node_of(hg, kind)), bw, probes_of(hg, kind), limit
+    return make
+
+
+def _one_bucket(hg, kind, n, j=17, order=None):
+    keys = sorted(hg.K((), j, k) for k in range(n))
+    if order is not None:
+        keys = [keys[i] for i in order]
+    return keys, hg.build_node({j: hg.bucket([(k, hg.val(kind, k)) for k in keys])})
+
+
+def _big_bucket(n):
+    def probes(hg, kind):
+        keys, _ = _one_bucket(hg, kind, n)
+        return [(keys[0], TRUE, hg.val(kind, keys[0])), (keys[-1], TRUE, hg.val(kind, keys[-1])),
+                (keys[n // 2], TRUE, hg.val(kind, keys[n // 2])), (hg.K((), 17, n), NOT_FOUND, None)]
+    return _get_case(lambda hg, kind: _one_bucket(hg, kind, n)[1], probes, limit=("bucket", n))
+
+
+def _node_of_97(hg, kind):
+    """31 buckets of 3 and one of 4 on child indices 0 … 31: 97 pairs"""
+    at, pairs = {}, []
+    for j in range(32):
+        keys = sorted(hg.K((), j, k) for k in range(4 if j == 31 else 3))
+        at[j] = hg.bucket([(k, hg.val(kind, k)) for k in keys])
+        pairs += keys
+    return hg.build_node(at), pairs
+
+
+def _respelled_key(spell):
+    """a node whose one bucket holds [key, value] with the KEY's head spelled by `spell(len)`; the key is found by its bytes"""
+    def node_of(hg, kind):
+        k = hg.K((), 17)
+        return hg.build_node({17: array([array([spell(len(k)) + k, hg.val(kind, k)])])})
+    return _get_case(node_of, lambda hg, kind: [(hg.K((), 17), TRUE, hg.val(kind, hg.K((), 17))), (hg.K((), 17, 1), NOT_FOUND, None)])
+
+
+def _respelled_actor(field):
+    def make(kind):
+        if kind == "vec_u8":
+            return None
+        hg = _hg()
+        i = hg.vi(hg.K((), 17))
+        v = hg.astate(i, seq=b"\x18\x05") if field == "sequence" else hg.astate(i, adr=b"\x58\x15\x01" + bytes(range(20)))
+        st = pyamt.Store()
+        return st, st.put(hg.build_node({17: hg.bucket([(hg.K((), 17), v)])})), 5, [(hg.K((), 17), TRUE, v)], None
+    return make
+
+
+def _width_out_of_range(bw):
+    def make(kind):
+        hg = _hg()
+        keys, items = hg.width_items(kind)
+        st = pyamt.Store()
+        root = hg.pyhamt.build_hamt(st, items, 5)
+        return st, root, bw, [(keys[0], ERR_DECODE, None), (b"no such key", ERR_DECODE, None)], ("width", bw)
+    return make
+
+
+def _counts(bits, n_pointers):
+    """a width-5 node whose bitfield has `bits` set over n_pointers one-pair buckets (for the lowest set bits, in order)"""
+    def node_of(hg, kind):
+        ptrs = [hg.bucket([(hg.K((), j), hg.val(kind, hg.K((), j)))]) for j in (list(bits) + [30, 31])[:n_pointers]]
+        return hg.node(sum(1 << j for j in bits), ptrs)
+    return node_of
+
+
+HAMT_GET_CASES = {
+    # HAMT_POINTER_COUNT_IS_CHECKED_WHEN_INDEXED: an Err only for the key that lands on the pointer that is not there
+    "popcount_above_the_pointer_count": _get_case(_counts((2, 9, 20), 2), lambda hg, kind: [
+        (hg.K((), 2), TRUE, hg.val(kind, hg.K((), 2))), (hg.K((), 9), TRUE, hg.val(kind, hg.K((), 9))),
+        (hg.K((), 20), ERR_DECODE, None), (hg.K((), 5), NOT_FOUND, None)]),
+    "popcount_below_the_pointer_count": _get_case(_counts((2, 9), 3), lambda hg, kind: [
+        (hg.K((), 2), TRUE, hg.val(kind, hg.K((), 2))), (hg.K((), 9), TRUE, hg.val(kind, hg.K((), 9))),
+        (hg.K((), 30), NOT_FOUND, None), (hg.K((), 5), NOT_FOUND, None)]),
+    "empty_bitfield_over_a_pointer": _get_case(_counts((), 1), lambda hg, kind: [(hg.K((), 30), NOT_FOUND, None), (hg.K((), 0), NOT_FOUND, None)]),
+    # HAMT_BUCKET_SIZE_AND_ORDER_ARE_NOT_CHECKED_ON_READ: the bucket is searched as it stands, the first match wins
+    "node_of_97_entries": _get_case(lambda hg, kind: _node_of_97(hg, kind)[0], lambda hg, kind: [
+        (_node_of_97(hg, kind)[1][0], TRUE, hg.val(kind, _node_of_97(hg, kind)[1][0])),
+        (_node_of_97(hg, kind)[1][-1], TRUE, hg.val(kind, _node_of_97(hg, kind)[1][-1])),
+        (hg.K((), 31, 4), NOT_FOUND, None)], limit=("entries", 97)),
+    "one_bucket_of_97_entries": _big_bucket(97),
+    "one_bucket_of_256_entries": _big_bucket(256),
+    "empty_bucket": _get_case(lambda hg, kind: hg.build_node({17: array([])}), lambda hg, kind: [(hg.K((), 17), NOT_FOUND, None), (hg.K((), 3), NOT_FOUND, None)]),
+    "unsorted_bucket": _get_case(lambda hg, kind: _one_bucket(hg, kind, 3, order=(2, 0, 1))[1],
+                                 lambda hg, kind: [(k, TRUE, hg.val(kind, k)) for k in _one_bucket(hg, kind, 3)[0]] + [(hg.K((), 17, 3), NOT_FOUND, None)]),
+    "same_key_twice_the_first_wins": _get_case(
+        lambda hg, kind: hg.build_node({17: hg.bucket([(hg.K((), 17), hg.val(kind, b"first")), (hg.K((), 17), hg.val(kind, b"second"))])}),
+        lambda hg, kind: [(hg.K((), 17), TRUE, hg.val(kind, b"first"))]),
+    # HAMT_BIT_WIDTH_OUTSIDE_1_TO_8_IS_AN_ERR_OF_THE_GET, on a root that exists (a missing root is 65 by the reference's own
+    # text: tests/hamt_get_cases.py width_*_root_missing)
+    **{f"width_{bw}_on_a_root_that_exists": _width_out_of_range(bw) for bw in (0, 9, 32, (1 << 32) - 1)},
+    # a non-minimal head is accepted (nonminimal_uint_argument_is_accepted above), also where a fast parse expects the short one
+    "key_head_58_nn_below_24": _respelled_key(lambda n: bytes([0x58, n])),
+    "key_head_59_00_nn": _respelled_key(lambda n: bytes([0x59, 0, n])),
+    "actor_state_sequence_spelled_18_05": _respelled_actor("sequence"),
+    "actor_state_address_header_58_15": _respelled_actor("address"),
+}
+
+
 # --- fvm_ipld_amt and fvm_shared as the EVENT chain meets them (tests/event_chain_cases.py `tipset`) ----------------------------
 # Each case: name → callable → (store, claim fields, expected status of verify_event_proof).  tests/pyevents.py names each
 # assumption with a constant and makes the choice the oracle and the engine were written to make; a case here pins what the

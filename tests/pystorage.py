@@ -328,6 +328,8 @@ def check_actor_state(x):
     _cid(a[1], "state")
     _u64(a[2], "sequence")
     bal = _bytes(a[3], "balance")  # BigInt bytes: empty for zero, else a sign byte 00 / 01 and the magnitude
+    if len(bal) > 128:
+        _bad("balance of more than 128 bytes")  # (fvm_shared's BigInt reader refuses a longer one)
     if bal and bal[0] > 1:
         _bad("balance sign")
     if a[4] is not None:
@@ -403,12 +405,14 @@ def _load_node(blocks, cid, check_value):
     return int.from_bytes(bf, "big"), pointers
 
 
-def hamt_get(blocks, root, bit_width, key, check_value):
-    """`Hamt::load_with_bit_width(root, store, bw)?.get(key)?` → the checked value, or None.
+def _hamt_find(blocks, root, bit_width, key, check_value):
+    """The walk of `Hamt::load_with_bit_width(root, store, bw)?.get(key)?` → (node block, pointer number, pair number,
+    checked value) of the pair that holds the key, or None.
     load reads the root block and nothing else — it does not look at the width (decode.rs:79-80: a missing root is the
     `?` of the load, whatever the width); get hashes the key and walks: at each node `HashBits::next(bw)`, bit clear ⇒
     None, else child number popcount(bits below); a link ⇒ load that node and go on; a bucket ⇒ linear search."""
-    bitfield, pointers = _load_node(blocks, root, check_value)
+    at = root
+    bitfield, pointers = _load_node(blocks, at, check_value)
     bits = _HashBits(key)
     while True:
         idx = bits.next(bit_width)
@@ -419,12 +423,49 @@ def hamt_get(blocks, root, bit_width, key, check_value):
             _bad("child index past the pointer list")  # HAMT_POINTER_COUNT_IS_CHECKED_WHEN_INDEXED
         child = pointers[below]
         if type(child) is Link:
-            bitfield, pointers = _load_node(blocks, child.cid, check_value)
+            at = child.cid
+            bitfield, pointers = _load_node(blocks, at, check_value)
             continue
-        for k, v in child:  # HAMT_BUCKET_SIZE_AND_ORDER_ARE_NOT_CHECKED_ON_READ
+        for n, (k, v) in enumerate(child):  # HAMT_BUCKET_SIZE_AND_ORDER_ARE_NOT_CHECKED_ON_READ
             if k == key:
-                return v
+                return blocks[at], below, n, v
         return None
+
+
+def hamt_get(blocks, root, bit_width, key, check_value):
+    """→ the checked value, or None"""
+    found = _hamt_find(blocks, root, bit_width, key, check_value)
+    return None if found is None else found[3]
+
+
+def _head(b, pos):
+    """the head of an item that is known to decode → (argument, position behind the head)"""
+    info = b[pos] & 31
+    if info < 24:
+        return info, pos + 1
+    nb = 1 << (info - 24)
+    return int.from_bytes(b[pos + 1:pos + 1 + nb], "big"), pos + 1 + nb
+
+
+def hamt_get_bytes(blocks, root, bit_width, key, check_value):
+    """`hamt_get`, answering with the value's own bytes as the node spells them (what the primitive ipcfp_hamt_get
+    LOCATES; the storage chain only ever needed the decoded value) → bytes, or None."""
+    found = _hamt_find(blocks, root, bit_width, key, check_value)
+    if found is None:
+        return None
+    b, pointer, pair, _ = found
+    _, pos = _head(b, 0)                 # [bitfield, pointers]
+    _, pos = _item(b, pos)
+    _, pos = _head(b, pos)
+    for _ in range(pointer):
+        _, pos = _item(b, pos)
+    _, pos = _head(b, pos)               # the bucket
+    for _ in range(pair):
+        _, pos = _item(b, pos)
+    _, pos = _head(b, pos)               # [key, value]
+    _, pos = _item(b, pos)
+    _, end = _item(b, pos)
+    return bytes(b[pos:end])
 
 
 # ---- read_storage_slot (storage/decode.rs:36-97) -----------------------------------------------------------------------
