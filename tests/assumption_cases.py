@@ -295,6 +295,10 @@ EVENT_CASES = {
     "events_root_height_8_at_bit_width_8_loads": lambda: _event_case(_root(bw=8, height=8, count=0, bitmap=bytes(32), values=[]), _claim_for(0), 11, 3),
     "events_root_height_9_at_bit_width_8": lambda: _event_case(_root(bw=8, height=9, count=0, bitmap=bytes(32), values=[]), _claim_for(0), ERR_DECODE, 4),
     "events_root_height_13_at_bit_width_5": lambda: _event_case(_root(height=13, count=0, bitmap=bytes(4), values=[]), _claim_for(0), ERR_DECODE, 5),
+    # … and at bit width 3, the width of every Amtv0 the enumerator walks (tests/amt_enum_cases.py "height_21_…", "height_22_…"):
+    # 64 / 3 = 21 loads, 22 is an Err of the load
+    "events_root_height_21_at_bit_width_3_loads": lambda: _event_case(_root(bw=3, height=21, count=0, bitmap=bytes(1), values=[]), _claim_for(0), 11, 15),
+    "events_root_height_22_at_bit_width_3": lambda: _event_case(_root(bw=3, height=22, count=0, bitmap=bytes(1), values=[]), _claim_for(0), ERR_DECODE, 16),
     # AMT_MAX_INDEX_IS_U64_MAX_MINUS_1: the generic Err (64) for u64::MAX, None for the index below it
     "event_index_u64_max": lambda: _event_case(_root(), _claim_for((1 << 64) - 1), 64, 6),
     "event_index_u64_max_minus_1": lambda: _event_case(_root(), _claim_for((1 << 64) - 2), 11, 7),

@@ -26,7 +26,7 @@ import hashlib
 import claims as claims_mod
 import pyamt
 import pystorage
-from pyamt import NULL, array, bstr, head, link, uint
+from pyamt import NULL, array, bstr, head, link, raw_root, uint  # noqa: F401  (raw_root: the cases' spelled roots)
 from event_spellings import data_bytes, entry, spelling_cases, stamped, text, topic  # noqa: F401  (spelling_cases: re-exported)
 from storage_chain_cases import cmap, encode, mutate_field, nint, store_of  # noqa: F401  (store_of: for the tests)
 
@@ -73,13 +73,6 @@ def good_event(emitter, topics=(0, 1), n_data=40) -> bytes:
 
 
 # ---- AMT roots the writer cannot lie about ------------------------------------------------------------------------------------
-def raw_root(store, values, bitmap: bytes, *, bw=5, height=0, count=None, links=(), trailer=b"", v0=False) -> bytes:
-    """a root block spelled field by field: `count` is the encoded item (default: the minimal uint of len(values))"""
-    node = array([bstr(bitmap), array([link(c) for c in links]), array(list(values))])
-    cnt = uint(len(values)) if count is None else count
-    return store.put(array(([] if v0 else [uint(bw)]) + [uint(height), cnt, node]) + trailer)
-
-
 def events_root(store, events: dict, bw=5, **kw) -> bytes:
     return pyamt.build_amt(store, events, version=3, bit_width=bw, **kw)
 

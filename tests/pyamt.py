@@ -2,6 +2,7 @@
 (sparse indices, lying counts, non-minimal heights).  Wire format per SURVEY.md A.5: v0 root
 `[height, count, node]` (bit width 3), v3 root `[bit_width, height, count, node]`, node
 `[bitmap bytes (LSB-first), [links…], [values…]]`, CID = CIDv1 dag-cbor blake2b-256."""
+import bisect
 import hashlib
 
 
@@ -66,32 +67,60 @@ class Store:
         return np.frombuffer(data, dtype=np.uint8).copy(), off, lens, c40
 
 
-def _node(store, bw, height, items, base, odd_links=()):
-    """items: sorted [(index, encoded value)] inside [base, base + W^(height+1)) → encoded node bytes.
-    odd_links: bases of child nodes that are linked through a sha2-256 CID instead of the standard one."""
+def raw_node(bitmap: bytes, links=(), values=(), *, links_head=None, values_head=None, trailer=b"") -> bytes:
+    """a node spelled field by field: `links` / `values` are ENCODED items; `links_head` / `values_head` replace the minimal
+    array head of that field (a two-byte form, a count that lies); `trailer` follows the node"""
+    lk = (head(4, len(links)) if links_head is None else links_head) + b"".join(links)
+    vl = (head(4, len(values)) if values_head is None else values_head) + b"".join(values)
+    return head(4, 3) + bstr(bitmap) + lk + vl + trailer
+
+
+def raw_root(store, values, bitmap: bytes, *, bw=5, height=0, count=None, links=(), trailer=b"", v0=False) -> bytes:
+    """a root block spelled field by field: `count` is the encoded item (default: the minimal uint of len(values))"""
+    node = array([bstr(bitmap), array([link(c) for c in links]), array(list(values))])
+    cnt = uint(len(values)) if count is None else count
+    return store.put(array(([] if v0 else [uint(bw)]) + [uint(height), cnt, node]) + trailer)
+
+
+def _node(store, bw, height, items, base, odd_links=(), lo=0, hi=None, where=None, respell=None):
+    """items: sorted [(index, encoded value)]; items[lo:hi] lie inside [base, base + W^(height+1)) → encoded node bytes.
+    odd_links: bases of child nodes that are linked through a sha2-256 CID instead of the standard one.
+    where: a dict that receives {(child height, child base): CID} of every block written.
+    respell: {(height, base): callable(bitmap, [encoded links], [encoded values]) → node bytes} for nodes spelled otherwise."""
+    hi = len(items) if hi is None else hi
     W = 1 << bw
     bmap = bytearray((W + 7) // 8)
     links, values = [], []
     if height == 0:
-        for i, v in items:
+        for i, v in items[lo:hi]:
             s = i - base
             bmap[s >> 3] |= 1 << (s & 7)
             values.append(v)
     else:
         span = W ** height
-        for s in range(W):
-            sub = [(i, v) for i, v in items if base + s * span <= i < base + (s + 1) * span]
-            if sub:
-                bmap[s >> 3] |= 1 << (s & 7)
-                child_base = base + s * span
-                child = _node(store, bw, height - 1, sub, child_base, odd_links)
-                links.append(link(store.put(child, sha256_cid=(height - 1, child_base) in odd_links)))
+        p = lo
+        while p < hi:
+            s = (items[p][0] - base) // span
+            child_base = base + s * span
+            q = bisect.bisect_left(items, (child_base + span,), p, hi)
+            if s >= W:  # (a height that lies low: what it cannot hold is left out)
+                break
+            bmap[s >> 3] |= 1 << (s & 7)
+            child = _node(store, bw, height - 1, items, child_base, odd_links, p, q, where, respell)
+            c = store.put(child, sha256_cid=(height - 1, child_base) in odd_links)
+            if where is not None:
+                where[(height - 1, child_base)] = c
+            links.append(link(c))
+            p = q
+    if respell and (height, base) in respell:
+        return respell[(height, base)](bytes(bmap), links, values)
     return array([bstr(bmap), array(links), array(values)])
 
 
-def build_amt(store, items, version=0, bit_width=3, height=None, count=None, odd_links=()):
-    """items: {index: encoded value}.  Returns the root CID.  `height` / `count` may lie.
-    odd_links: {(child height, child base index)} linked through a 36-byte sha2-256 CID."""
+def build_amt(store, items, version=0, bit_width=3, height=None, count=None, odd_links=(), where=None, respell=None, trailer=b""):
+    """items: {index: encoded value}.  Returns the root CID.  `height` / `count` may lie; `count` may be the ENCODED item
+    (bytes: a width of its own).  odd_links: {(child height, child base index)} linked through a 36-byte sha2-256 CID.
+    where / respell: see _node (the root node is (height, 0)); `trailer` follows the root block."""
     bw = 3 if version == 0 else bit_width
     W = 1 << bw
     srt = sorted(items.items())
@@ -101,9 +130,9 @@ def build_amt(store, items, version=0, bit_width=3, height=None, count=None, odd
         h += 1
     if height is not None:
         h = height
-    node = _node(store, bw, h, srt, 0, set(odd_links))
+    node = _node(store, bw, h, srt, 0, set(odd_links), where=where, respell=respell)
     cnt = len(srt) if count is None else count
-    root = array(([uint(bw)] if version != 0 else []) + [uint(h), uint(cnt), node])
+    root = array(([uint(bw)] if version != 0 else []) + [uint(h), cnt if isinstance(cnt, bytes) else uint(cnt), node]) + trailer
     return store.put(root)
 
 

@@ -228,18 +228,26 @@ def amt_get(a: Amt, i: int):
         nd, h, i = _amt_child(a, nd.links[nd.bits.index(sub)]), h - 1, i % span
 
 
-def amt_for_each(a: Amt):
-    """yields (index, checked value) in ascending index order, depth first — the first failure in that order is the Err"""
+def amt_for_each(a: Amt, lo=0, hi=None):
+    """yields (index, checked value) in ascending index order, depth first — the first failure in that order is the Err.
+    With a range [lo, hi): a subtree whose indices lie wholly outside it is not entered (its block is not fetched), and of
+    the values of a leaf that is entered those inside the range are yielded; nothing else changes — a node that IS entered is
+    decoded whole."""
+    def meets(base, span):
+        return hi is None or (base < hi and base + span > lo)
+
     def walk(nd, h, base):
         if not nd.links:
             for k, i in enumerate(nd.bits):
-                yield base + i, nd.values[k]
+                if meets(base + i, 1):
+                    yield base + i, nd.values[k]
             return
         if h == 0:
             _bad("links at height 0")
         span = 1 << min(a.bit_width * h, 64)
         for k, i in enumerate(nd.bits):
-            yield from walk(_amt_child(a, nd.links[k]), h - 1, base + i * span)
+            if meets(base + i * span, span):
+                yield from walk(_amt_child(a, nd.links[k]), h - 1, base + i * span)
     yield from walk(a.node, a.height, 0)
 
 
@@ -388,14 +396,16 @@ def reaches_step_4(blocks, c, trust=None) -> bool:
 
 
 # ---- find_matching_events (generator.rs:180-307), offline: the receipt list is the receipts AMT walked in index order ------
-def scan(blocks, receipts_root, topic0, topic1, actor=None):
-    """→ (status, has-match list, [(exec_index, event_index, emitter)] in emission order, set of recorded CIDs)"""
+def scan(blocks, receipts_root, topic0, topic1, actor=None, lo=0, hi=None):
+    """→ (status, has-match list, [(exec_index, event_index, emitter)] in emission order, set of recorded CIDs).
+    With a receipt range [lo, hi) (a shard of one tipset: include/ipcfp.h ipcfp_witness_create_subset): the receipt list is
+    `amt_for_each` under that range, and has[i - lo] is receipt i."""
     filt = (topic0, topic1)
     try:
         rec = set()
         r_amt = amt_load(blocks, receipts_root, 0, check_receipt, seen=rec)                  # :195-196
-        receipts = [(i, v) for i, v in amt_for_each(amt_load(blocks, receipts_root, 0, check_receipt))]  # :199-204 (the RPC list)
-        has = [0] * (max((i for i, _ in receipts), default=-1) + 1)
+        receipts = [(i, v) for i, v in amt_for_each(amt_load(blocks, receipts_root, 0, check_receipt), lo, hi)]  # :199-204 (the RPC list)
+        has = [0] * max(0, max((i for i, _ in receipts), default=-1) + 1 - lo)
 
         def wanted(ev):
             emitter, entries = ev
@@ -404,21 +414,40 @@ def scan(blocks, receipts_root, topic0, topic1, actor=None):
             log = extract_evm_log(entries)
             return log is not None and matches_log(log[0], filt)                              # :227-231
 
+        # (an events root that many receipts name is walked once per pass: the blocks do not change under a scan, so the walk's
+        # events, its Err and the CIDs it records are the same every time)
+        walked = {}
+
+        def events_of(root, seen):
+            key = (root, seen is not None)
+            if key not in walked:
+                mine = set() if seen is not None else None
+                try:
+                    walked[key] = (list(amt_for_each(amt_load(blocks, root, 3, check_stamped_event, seen=mine))), mine)
+                except Err as e:
+                    walked[key] = (e, mine)
+            out, mine = walked[key]
+            if seen is not None:
+                seen |= mine
+            if isinstance(out, Err):
+                raise out
+            return out
+
         matching = []
         for i, root in receipts:                                                              # PASS 1 (:209-239)
             if root is None:
                 continue
             hit = False
-            for _j, ev in amt_for_each(amt_load(blocks, root, 3, check_stamped_event)):
+            for _j, ev in events_of(root, None):
                 hit = wanted(ev) or hit
             if hit:
                 matching.append((i, root))
-                has[i] = 1
+                has[i - lo] = 1
         triples = []
         for i, root in matching:                                                              # PASS 2 (:242-301)
             if amt_get(r_amt, i) is ABSENT:
                 continue                                                                      # :249-251
-            for j, ev in amt_for_each(amt_load(blocks, root, 3, check_stamped_event, seen=rec)):
+            for j, ev in events_of(root, rec):
                 if wanted(ev):
                     triples.append((i, j, ev[0]))
         return TRUE, has, triples, rec

@@ -23,6 +23,8 @@ def run_scan(engine, oracle, store, root):
     assert gs == os_, (gs, os_)
     if gs == 1:
         assert np.array_equal(ghas, ohas) and len(gm) == len(otrip)
+        # the blocks the scan recorded (RecordingBlockStore, generator.rs:195-196): the oracle's, CID for CID
+        assert {bytes(c) for c in tabs[3][gids]} == {bytes(c) for c in otouched}
     return gs, ghas
 
 
