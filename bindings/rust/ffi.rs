@@ -56,6 +56,7 @@ pub const IPCFP_MAX_PARENTS: usize = 32;
 pub const IPCFP_ABI_VERSION: c_int = 3;
 pub const IPCFP_SCAN_PHASE_RECEIPTS: u32 = 1;
 pub const IPCFP_SCAN_PHASE_EVENTS: u32 = 2;
+pub const IPCFP_MAX_SCAN_SPECS: usize = 1024;
 pub const IPCFP_ST_TRUE: u8 = 1;
 pub const IPCFP_ST_FALSE_FILTER: u8 = 17;
 /// `ipcfp_check_event_fn` of the header: the host predicate of ipcfp_verify_event_proofs_with
@@ -564,6 +565,39 @@ impl Witness<'_> {
             blocks.push(ProofBlock { cid, data });
         }
         Ok(UnifiedProofBundle { storage_proofs, event_proofs, blocks })
+    }
+
+    /// `find_matching_events` for a SET of specs — (filter, optional emitter) as `EventProofSpec` holds them — in one
+    /// pass over the resident tipset (`ipcfp_scan_events_multi`, at most `IPCFP_MAX_SCAN_SPECS` specs).  Returns the
+    /// records in (exec_index, event_index, spec) order with the spec each belongs to, and the per-spec totals: the
+    /// records with `spec == j`, in order, are what a single-filter scan of spec j returns.  Err: the scan's status, which
+    /// does not depend on the specs.
+    pub fn scan_events_multi(&self, receipts_root: &Cid, specs: &[(ipcfp_event_filter_t, Option<u64>)])
+                             -> Result<(Vec<ipcfp_event_match_t>, Vec<u32>, Vec<u64>)> {
+        if specs.is_empty() || specs.len() > IPCFP_MAX_SCAN_SPECS { return Err(anyhow!("scan_events_multi takes 1 to {IPCFP_MAX_SCAN_SPECS} specs")); }
+        let root = cid_slot(receipts_root)?;
+        let filters: Vec<ipcfp_event_filter_t> = specs.iter().map(|s| s.0).collect();
+        let has: Vec<u8> = specs.iter().map(|s| s.1.is_some() as u8).collect();
+        let actors: Vec<u64> = specs.iter().map(|s| s.1.unwrap_or(0)).collect();
+        let n = specs.len() as u32;
+        let (mut st, mut nr, mut nm) = (0u8, 0u64, 0u64);
+        let mut counts = vec![0u64; specs.len()];
+        let rc = unsafe { ipcfp_scan_events_multi(self.eng.ctx, self.raw(), root.as_ptr(), filters.as_ptr(), has.as_ptr(), actors.as_ptr(), n, &mut st,
+                                                  std::ptr::null_mut(), 0, &mut nr, std::ptr::null_mut(), std::ptr::null_mut(), 0, &mut nm,
+                                                  counts.as_mut_ptr(), std::ptr::null_mut()) };
+        if rc != 0 { return Err(self.eng.err("ipcfp_scan_events_multi", rc)); }
+        if st != IPCFP_ST_TRUE { return Err(anyhow!("find_matching_events failed with status {st}")); }
+        let cap = nm as usize;
+        let mut matches = vec![unsafe { std::mem::zeroed::<ipcfp_event_match_t>() }; cap];
+        let mut match_spec = vec![0u32; cap];
+        if cap > 0 {
+            let rc = unsafe { ipcfp_scan_events_multi(self.eng.ctx, self.raw(), root.as_ptr(), filters.as_ptr(), has.as_ptr(), actors.as_ptr(), n, &mut st,
+                                                      std::ptr::null_mut(), 0, &mut nr, matches.as_mut_ptr(), match_spec.as_mut_ptr(), cap as u64, &mut nm,
+                                                      counts.as_mut_ptr(), std::ptr::null_mut()) };
+            if rc != 0 { return Err(self.eng.err("ipcfp_scan_events_multi", rc)); }
+            if st != IPCFP_ST_TRUE { return Err(anyhow!("find_matching_events failed with status {st}")); }
+        }
+        Ok((matches, match_spec, counts))
     }
 
     /// `generate_event_proof` for one filter (src/proofs/events/generator.rs:75-178): the `EventProof`s of

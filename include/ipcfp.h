@@ -188,7 +188,10 @@ enum {
     IPCFP_K_SGEN_RUNS = 19,       /* ipcfp_generate_storage_claims*: run discovery and the per-run chain (header … layout sniff) */
     IPCFP_K_SGEN_SPECS = 20,      /* … the per-spec storage get: value, cflags, status (table kernel + one-lane kernel) */
     IPCFP_K_SGEN_RECORDS = 21,    /* … the 192-byte run records */
-    IPCFP_K_COUNT = 22
+    IPCFP_K_SCAN_MULTI_COUNT = 22, /* ipcfp_scan_events_multi*: PASS 1 for a set of specs (records probed against the filter set) */
+    IPCFP_K_SCAN_MULTI_FILL = 23,  /* … PASS 2: the has-map, matches + match_spec, per-spec counts */
+    IPCFP_K_SCAN_MULTI_TAIL = 24,  /* … the table route's tail in one launch: look-back prefix sum, map, fill, counts, mailbox */
+    IPCFP_K_COUNT = 25
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -388,6 +391,37 @@ int ipcfp_scan_events_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t
 #define IPCFP_SCAN_PHASE_RECEIPTS 1
 #define IPCFP_SCAN_PHASE_EVENTS 2
 int ipcfp_witness_last_scan_phase(const ipcfp_witness_t* w);
+
+/* ipcfp_scan_events for a SET of specs in one pass over the resident tipset: spec j is filters[j] plus, where
+ * has_actor[j] != 0, the emitter actors[j] (`generate_proof_bundle`'s event_specs, src/proofs/generator.rs:18-22,58-78).
+ *   has_actor          n_specs bytes, or NULL: no spec filters by emitter; actors[j] is read only where has_actor[j] != 0
+ *   receipt_has_match  (nullable) byte r = 1 ⇔ receipt r has a match of SOME spec; *n_receipts as ipcfp_scan_events
+ *   matches/match_spec (nullable, together) up to cap_matches records and the spec each belongs to, in ascending
+ *                      (exec_index, event_index) order and, for one event that matches several specs, in ascending spec
+ *                      index.  So the stable selection match_spec == j IS the match list of ipcfp_scan_events with spec
+ *                      j.  Identical specs, and specs that differ only in the emitter filter, each yield their own records.
+ *   *n_matches         the total over all specs, whatever the cap (cap_matches == 0 or matches == NULL: a sizing call)
+ *   spec_counts        (nullable) n_specs totals, never truncated: spec_counts[j] is spec j's n_matches
+ *   touched_bits       (nullable) as ipcfp_scan_events, for "the receipt matches any spec": the union of the specs' recorders
+ * *status_out and ipcfp_witness_last_scan_phase are what a single-filter call gives (a scan's Err does not depend on its
+ * filter); on an Err nothing else is written.  The witness's receipt range applies.  n_specs == 0 or a null mandatory
+ * pointer: IPCFP_E_INVALID; n_specs > IPCFP_MAX_SCAN_SPECS or a total of 2^32 - 1 matches or more: IPCFP_E_UNSUPPORTED.
+ * The call leaves the state of the single-filter calls alone (their cached per-filter counts, the block table's filter):
+ * a later ipcfp_scan_events* answers as it would have without it.                                                        */
+#define IPCFP_MAX_SCAN_SPECS 1024
+int ipcfp_scan_events_multi(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* receipts_root40,
+                            const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                            uint32_t n_specs, ipcfp_status_t* status_out, uint8_t* receipt_has_match, uint64_t cap_receipts,
+                            uint64_t* n_receipts, ipcfp_event_match_t* matches, uint32_t* match_spec, uint64_t cap_matches,
+                            uint64_t* n_matches, uint64_t* spec_counts, uint32_t* touched_bits);
+/* … with DEVICE outputs: receipt_has_match_d (cap_receipts bytes), matches_d (cap_matches ipcfp_event_match_t),
+ * match_spec_d (cap_matches uint32) and spec_counts_d (n_specs uint64) are HBM buffers of the caller (nullable);
+ * summary_d as ipcfp_scan_events_device has it.  The filters, has_actor and actors are host arrays.               */
+int ipcfp_scan_events_multi_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* receipts_root40,
+                                   const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                                   uint32_t n_specs, ipcfp_status_t* status_out, void* receipt_has_match_d,
+                                   uint64_t cap_receipts, uint64_t* n_receipts, void* matches_d, void* match_spec_d,
+                                   uint64_t cap_matches, uint64_t* n_matches, void* spec_counts_d, void* summary_d);
 
 /* ---- proof claims (string form, exactly the reference's structs) ----------
  * CIDs and hex values are NUL-terminated strings, as in the reference's serde

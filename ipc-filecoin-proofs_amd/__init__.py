@@ -25,6 +25,7 @@ from .binding import (  # noqa: F401
     CID_MISMATCH,
     CID_UNCHECKED,
     KERNEL_IDS,
+    MAX_SCAN_SPECS,
     pack_event_claims,
     pack_storage_claims,
     SCLAIM_DTYPE,

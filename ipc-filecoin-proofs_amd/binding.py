@@ -15,6 +15,7 @@ __all__ = [
     "ABI_VERSION",
     "SCAN_PHASE_RECEIPTS",
     "SCAN_PHASE_EVENTS",
+    "MAX_SCAN_SPECS",
     "merge_scan_status",
     "host_register",
     "ingest_buffer",
@@ -102,7 +103,12 @@ KERNEL_IDS = {
     "sgen_runs": 19,
     "sgen_specs": 20,
     "sgen_records": 21,
+    "scan_multi_count": 22,
+    "scan_multi_fill": 23,
+    "scan_multi_tail": 24,
 }
+
+MAX_SCAN_SPECS = 1024
 
 
 class ST:
@@ -415,6 +421,8 @@ def load_library() -> C.CDLL:
         "ipcfp_unpacked_storage_destroy": (None, [vp]),
         "ipcfp_bundle_write_claims_json": (i32, [vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
         "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
+        "ipcfp_scan_events_multi": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
+        "ipcfp_scan_events_multi_device": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -1569,6 +1577,72 @@ class Witness:
                                                           has_ptr or None, int(cap_receipts), C.byref(nr),
                                                           matches_ptr or None, int(cap_matches), C.byref(nm),
                                                           summary_ptr or None), "scan_events_device")
+        return int(st[0]), int(nr.value), int(nm.value)
+
+    @staticmethod
+    def _scan_specs(specs):
+        """[(topic0, topic1, actor or None)] → (filters u8[n, 64], has_actor u8[n], actors u64[n])"""
+        filt = np.zeros((len(specs), 64), dtype=np.uint8)
+        has = np.zeros(len(specs), dtype=np.uint8)
+        actors = np.zeros(len(specs), dtype=np.uint64)
+        for j, (t0, t1, actor) in enumerate(specs):
+            key = bytes(t0) + bytes(t1)
+            if len(key) != 64:
+                raise ValueError(f"spec {j}: topic0 and topic1 are 32 bytes each")
+            filt[j] = np.frombuffer(key, dtype=np.uint8)
+            if actor is not None:
+                has[j], actors[j] = 1, int(actor)
+        return filt, has, actors
+
+    def scan_events_multi(self, receipts_root: bytes, specs, want_touched=True, cap_matches=None):
+        """The scan for a SET of specs [(topic0, topic1, actor or None)] in one pass (ipcfp_scan_events_multi).
+        → (status, has_match u8[n_receipts] — some spec matches —, matches structured[n], match_spec u32[n], spec_counts
+        u64[n_specs], touched block ids, per_spec) where per_spec[j] = matches[match_spec == j], spec j's own match list.
+        cap_matches: at most that many records come back (the counts stay the full ones); None: all of them."""
+        root = cid_slots([receipts_root])[0].copy()
+        filt, has_a, actors = self._scan_specs(specs)
+        n = len(specs)
+        st = np.zeros(1, dtype=np.uint8)
+        nr, nm = C.c_uint64(), C.c_uint64()
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+
+        def call(has, m, ms, touched):
+            self.eng._check(self.lib.ipcfp_scan_events_multi(self.eng.h, self.h, _p(root), _p(filt), _p(has_a), _p(actors), n, _p(st),
+                                                             _p(has), 0 if has is None else len(has), C.byref(nr),
+                                                             _p(m), _p(ms), 0 if m is None else len(m), C.byref(nm),
+                                                             _p(counts), _p(touched)), "scan_events_multi")
+
+        call(None, None, None, None)  # the sizing call
+        if st[0] != 1:
+            return int(st[0]), None, None, None, None, None, None
+        total = int(nm.value)
+        take = total if cap_matches is None else min(total, int(cap_matches))
+        has = np.zeros(int(nr.value), dtype=np.uint8)
+        m = np.zeros(take, dtype=MATCH_DTYPE) if take else None
+        ms = np.zeros(take, dtype=np.uint32) if take else None
+        touched = np.zeros(max((self.n + 31) // 32, 1), dtype=np.uint32) if want_touched else None
+        call(has, m, ms, touched)
+        m = np.zeros(0, dtype=MATCH_DTYPE) if m is None else m
+        ms = np.zeros(0, dtype=np.uint32) if ms is None else ms
+        ids = None
+        if want_touched:
+            ids = np.nonzero(np.unpackbits(touched.view(np.uint8), bitorder="little")[: self.n])[0]
+        per_spec = [m[ms == j] for j in range(n)]
+        return int(st[0]), has, m, ms, counts[:n].copy(), ids, per_spec
+
+    def scan_events_multi_device(self, receipts_root: bytes, specs, has_ptr: int = 0, cap_receipts: int = 0, matches_ptr: int = 0,
+                                 match_spec_ptr: int = 0, cap_matches: int = 0, spec_counts_ptr: int = 0, summary_ptr: int = 0):
+        """ipcfp_scan_events_multi_device: the map, the records, match_spec and the per-spec counts stay in HBM (pointers of
+        the caller, 0: not wanted).  → (status, n_receipts, n_matches)"""
+        root = cid_slots([receipts_root])[0].copy()
+        filt, has_a, actors = self._scan_specs(specs)
+        st = np.zeros(1, dtype=np.uint8)
+        nr, nm = C.c_uint64(), C.c_uint64()
+        self.eng._check(self.lib.ipcfp_scan_events_multi_device(self.eng.h, self.h, _p(root), _p(filt), _p(has_a), _p(actors), len(specs),
+                                                                _p(st), has_ptr or None, int(cap_receipts), C.byref(nr),
+                                                                matches_ptr or None, match_spec_ptr or None, int(cap_matches),
+                                                                C.byref(nm), spec_counts_ptr or None, summary_ptr or None),
+                        "scan_events_multi_device")
         return int(st[0]), int(nr.value), int(nm.value)
 
     # -- generator side -------------------------------------------------------------------------

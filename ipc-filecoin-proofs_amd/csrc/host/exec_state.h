@@ -96,6 +96,8 @@ int verify_packed_fast(ipcfp_ctx* ctx, ipcfp_witness* w, std::vector<TipsetCtxDe
 ScanParams scan_params_of(const ipcfp_event_filter_t& filter, int has_actor, uint64_t actor);
 // the look-back state of k_scan_tail_fused for n_tiles tiles (context-owned; zeroed when (re)allocated)
 int scan_tail_scratch(ipcfp_ctx* ctx, uint32_t n_tiles, unsigned long long** out);
+// the host's side of the mailbox: spin until the device has published sequence number `seq` (host/scan_events.cpp)
+int mailbox_wait(ipcfp_ctx* ctx, unsigned long long seq, const char* what);
 
 // `cap_matches`: how many matches the caller can take.  With a known capacity PASS 2 is launched right behind
 // PASS 1 (the kernel clips its writes) and the scan has ONE synchronisation; with kAllMatches the match count is

@@ -24,6 +24,7 @@
 #include "../kernels/launch.h"
 #include "../kernels/storage_runs.h"
 #include "exec_state.h"
+#include "scan_events_multi.h"
 #include "tipset_wide.h"
 
 using namespace ipcfp;
@@ -143,44 +144,75 @@ struct EventGenCore {
     uint64_t nm = 0;
 };
 
+// Steps 1-4 of generate_event_proof (generator.rs:89-135), one text for the single-spec core and the bundle's one pass: the
+// recorder (the bitmap + two flag words), the child header → receipts root, then parent headers, TxMeta, the message AMTs
+// (recorded) and the execution order with verify_txmeta = false.  One traversal serves record_transaction_amts and
+// build_execution_order: both load exactly the same blocks in the same order.
+struct EventGenOrder {
+    uint32_t status = IPCFP_ST_ERR;  // != TRUE: the Err of these steps (nothing else is then meaningful)
+    uint32_t words = 0;              // of the bitmap
+    uint32_t* oor_d = nullptr;       // flag: an exec_index is outside the execution order
+    uint32_t* missing_d = nullptr;   // flag: a base CID is absent from the store
+    DevBuf<TipsetCtxDev> tc_d;
+    ExecState ex;
+};
+
+int event_gen_order(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent_cids40, uint32_t n_parents, const uint8_t* child_cid40,
+                    DevBuf<uint32_t>& touched, TipsetCtxDev& tc, WideParents& wide, EventGenOrder& o) {
+    o.status = IPCFP_ST_ERR;
+    o.words = div_up(uint32_t(w->n), 32);
+    IPCFP_HIP(ctx, touched.alloc(o.words + 2));
+    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(o.words + 2) * 4, ctx->stream));
+    o.oor_d = touched.p + o.words;
+    o.missing_d = touched.p + o.words + 1;
+    const WitnessView rec = witness_view(w, touched.p);
+    // Step 1 (generator.rs:89-95): child header → receipts root.  The context kernel also loads parent 0.
+    if (int rc_t = tipset_inputs_list(ctx, TC_PARENTS_PARSED | TC_CHILD_PARSED, parent_cids40, n_parents, child_cid40, tc, wide)) return rc_t;
+    IPCFP_HIP(ctx, o.tc_d.alloc(1));
+    IPCFP_HIP(ctx, hipMemcpyAsync(o.tc_d.p, &tc, sizeof tc, hipMemcpyHostToDevice, ctx->stream));
+    int rc = launch_ctx_headers(ctx, rec, o.tc_d.p);
+    if (rc) return rc;
+    IPCFP_HIP(ctx, d2h_small(ctx, &tc, o.tc_d.p, sizeof tc, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    if (tc.child_status != IPCFP_ST_TRUE) {
+        o.status = tc.child_status;
+        return IPCFP_OK;
+    }
+    // Steps 2-4 (generator.rs:97-135)
+    rc = build_exec_order(ctx, rec, o.tc_d.p, n_parents, o.ex, /*verify_txmeta=*/0);
+    if (rc) return rc;
+    o.status = o.ex.status;
+    return IPCFP_OK;
+}
+
+// base witness (generator.rs:97-112): parents, child, receipts root (TxMeta CIDs were marked by the traversal).  Queued;
+// base_d is read until the caller's next synchronisation.
+int event_gen_mark_base(ipcfp_ctx* ctx, ipcfp_witness* w, DevBuf<uint32_t>& touched, const TipsetCtxDev& tc, const WideParents& wide,
+                        uint32_t* missing_d, std::vector<CidKey>& base, DevBuf<CidKey>& base_d) {
+    tipset_parent_keys(tc, wide, base);
+    base.push_back(tc.child);
+    base.push_back(tc.receipts_root);
+    IPCFP_HIP(ctx, base_d.alloc(base.size()));
+    IPCFP_HIP(ctx, hipMemcpyAsync(base_d.p, base.data(), base.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
+    return launch_mark_cids(ctx, witness_view(w, touched.p), base_d.p, uint32_t(base.size()), missing_d);
+}
+
 // Steps 1-6 of generate_event_proof and the base witness marks.  IPCFP_OK with core.status != IPCFP_ST_TRUE: the Err the
 // reference's `?` surfaces first (nothing else of `core` is then meaningful).
 int generate_events_core(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent_cids40, uint32_t n_parents, const uint8_t* child_cid40,
                          const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor, EventGenCore& core) {
     core.status = IPCFP_ST_ERR;
-    const uint32_t words = div_up(uint32_t(w->n), 32);
     DevBuf<uint32_t>& touched = core.touched;
-    IPCFP_HIP(ctx, touched.alloc(words + 2));
-    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words + 2) * 4, ctx->stream));
-    uint32_t* oor_d = touched.p + words;          // an exec_index is outside the execution order
-    uint32_t* missing_d = touched.p + words + 1;  // a base CID is absent from the store
-    const WitnessView rec = witness_view(w, touched.p);
-
-    // Step 1 (generator.rs:89-95): child header → receipts root.  The context kernel also loads parent 0.
     TipsetCtxDev& tc = core.tc;
-    WideParents& wide = core.wide;
-    if (int rc_t = tipset_inputs_list(ctx, TC_PARENTS_PARSED | TC_CHILD_PARSED, parent_cids40, n_parents, child_cid40, tc, wide)) return rc_t;
-    DevBuf<TipsetCtxDev> tc_d;
-    IPCFP_HIP(ctx, tc_d.alloc(1));
-    IPCFP_HIP(ctx, hipMemcpyAsync(tc_d.p, &tc, sizeof tc, hipMemcpyHostToDevice, ctx->stream));
-    int rc = launch_ctx_headers(ctx, rec, tc_d.p);
+    EventGenOrder order;
+    int rc = event_gen_order(ctx, w, parent_cids40, n_parents, child_cid40, touched, tc, core.wide, order);
     if (rc) return rc;
-    IPCFP_HIP(ctx, d2h_small(ctx, &tc, tc_d.p, sizeof tc, ctx->stream));
-    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
-    if (tc.child_status != IPCFP_ST_TRUE) {
-        core.status = tc.child_status;
+    if (order.status != IPCFP_ST_TRUE) {
+        core.status = order.status;
         return IPCFP_OK;
     }
-    // Steps 2-4 (generator.rs:97-135): parent headers, TxMeta, the message AMTs (recorded) and the
-    // execution order with verify_txmeta = false.  One traversal serves record_transaction_amts and
-    // build_execution_order: both load exactly the same blocks in the same order.
-    ExecState ex;
-    rc = build_exec_order(ctx, rec, tc_d.p, n_parents, ex, /*verify_txmeta=*/0);
-    if (rc) return rc;
-    if (ex.status != IPCFP_ST_TRUE) {
-        core.status = ex.status;
-        return IPCFP_OK;
-    }
+    ExecState& ex = order.ex;
+    uint32_t* const oor_d = order.oor_d;
     // Step 5 (generator.rs:137-150): two-pass scan, recording
     ScanResult& scan = core.scan;
     rc = scan_events_device(ctx, w, tc.receipts_root, *filter, has_actor, actor, touched.p, scan);
@@ -205,15 +237,9 @@ int generate_events_core(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent
         rc = launch_gather_keys(ctx, exec_list.p, ex.exec_len, exec_idx.p, uint32_t(nm), core.msg.p, oor_d);
         if (rc) return rc;
     }
-    // base witness (generator.rs:97-112): parents, child, receipts root (TxMeta CIDs were marked by the traversal)
     std::vector<CidKey> base;
-    tipset_parent_keys(tc, wide, base);
-    base.push_back(tc.child);
-    base.push_back(tc.receipts_root);
     DevBuf<CidKey> base_d;
-    IPCFP_HIP(ctx, base_d.alloc(base.size()));
-    IPCFP_HIP(ctx, hipMemcpyAsync(base_d.p, base.data(), base.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_mark_cids(ctx, rec, base_d.p, uint32_t(base.size()), missing_d);
+    rc = event_gen_mark_base(ctx, w, touched, tc, core.wide, order.missing_d, base, base_d);
     if (rc) return rc;
     uint32_t flag[2] = {0, 0};
     IPCFP_HIP(ctx, d2h_small(ctx, flag, oor_d, 8, ctx->stream));
@@ -228,6 +254,97 @@ int generate_events_core(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent
     }
     core.nm = nm;
     core.status = IPCFP_ST_TRUE;
+    return IPCFP_OK;
+}
+
+// generate_event_proof for ALL event specs of a bundle in one pass (src/proofs/generator.rs:58-78 runs it spec by spec):
+// steps 1-4 — headers, TxMeta, message AMTs, execution order — ONCE, one recorder, one scan per ≤ IPCFP_MAX_SCAN_SPECS
+// specs (host/scan_events_multi.cpp), one gather of message CIDs per scan.  What is common to every spec (a header, the
+// execution order, the scan's status, a missing base CID) fails spec 0; "Missing message at index" (events/generator.rs:
+// 244-246) fails exactly the specs that have a match at a receipt index beyond the execution order.
+struct BundleEvents {
+    uint32_t common_status = IPCFP_ST_ERR;  // != TRUE: the Err every spec's generate_event_proof surfaces first
+    bool missing_base = false;              // must_get of a base CID fails (witness.rs:45-48): after a spec's own Err
+    std::vector<uint8_t> spec_oor;          // spec j has a match outside the execution order
+    std::vector<ipcfp_event_match_t> matches;  // scan order, chunk by chunk
+    std::vector<uint32_t> match_spec;          // global spec index
+    std::vector<uint8_t> msg;                  // IPCFP_CID_SLOT bytes per match
+    std::vector<uint32_t> block_ids;           // the recorder's blocks, ascending ids
+};
+
+int generate_bundle_events(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* parent_cids40, uint32_t n_parents, const uint8_t* child_cid40,
+                           const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors, uint64_t n_specs,
+                           BundleEvents& out) {
+    IPCFP_ENTER(ctx);
+    out.common_status = IPCFP_ST_ERR;
+    out.spec_oor.assign(n_specs, 0);
+    DevBuf<uint32_t> touched;
+    TipsetCtxDev tc;
+    WideParents wide;
+    EventGenOrder order;
+    int rc = event_gen_order(ctx, w, parent_cids40, n_parents, child_cid40, touched, tc, wide, order);
+    if (rc) return rc;
+    if (order.status != IPCFP_ST_TRUE) {
+        out.common_status = order.status;
+        return IPCFP_OK;
+    }
+    ExecState& ex = order.ex;
+    const uint32_t words = order.words;
+    DevBuf<CidKey> exec_list;
+    bool have_list = false;
+    // Steps 5 and 6 per chunk of specs: the scan on the one recorder, then message CID of each match = exec_list[exec_index]
+    for (uint64_t first = 0; first < n_specs; first += IPCFP_MAX_SCAN_SPECS) {
+        const uint32_t n_chunk = uint32_t(n_specs - first < IPCFP_MAX_SCAN_SPECS ? n_specs - first : IPCFP_MAX_SCAN_SPECS);
+        MultiScanResult scan;
+        rc = scan_events_multi_device(ctx, w, tc.receipts_root, filters + first, has_actor + first, actors + first, n_chunk, touched.p, scan,
+                                      kAllMatches);
+        if (rc) return rc;
+        if (scan.status != IPCFP_ST_TRUE) {  // (the same for every chunk: a scan's status does not depend on its specs)
+            out.common_status = scan.status;
+            return IPCFP_OK;
+        }
+        const uint64_t nm = scan.n_matches;
+        if (nm == 0) continue;
+        if (out.matches.size() + nm >= 0xffffffffULL) return set_error(ctx, IPCFP_E_UNSUPPORTED, "too many matches");
+        DevBuf<CidKey> msg_d;
+        DevBuf<uint64_t> exec_idx;
+        if (!have_list) {
+            IPCFP_HIP(ctx, exec_list.alloc(ex.exec_len ? ex.exec_len : 1));
+            rc = launch_exec_compact(ctx, ex.keys.p, uint32_t(ex.raw_len), ex.first.p, ex.pos.p, exec_list.p);
+            if (rc) return rc;
+            have_list = true;
+        }
+        IPCFP_HIP(ctx, msg_d.alloc(nm));
+        IPCFP_HIP(ctx, hipMemsetAsync(msg_d.p, 0, nm * sizeof(CidKey), ctx->stream));
+        IPCFP_HIP(ctx, exec_idx.alloc(nm));
+        rc = launch_match_exec_index(ctx, scan.matches_p, uint32_t(nm), exec_idx.p);
+        if (rc) return rc;
+        rc = launch_gather_keys(ctx, exec_list.p, ex.exec_len, exec_idx.p, uint32_t(nm), msg_d.p, order.oor_d);  // (the flag is the gather's own:
+        if (rc) return rc;                                                                                    //  the per-spec verdict is read off the records below)
+        const size_t at = out.matches.size();
+        out.matches.resize(at + nm);
+        out.match_spec.resize(at + nm);
+        out.msg.resize((at + nm) * IPCFP_CID_SLOT);
+        IPCFP_HIP(ctx, hipMemcpyAsync(out.matches.data() + at, scan.matches_p, nm * sizeof(ipcfp_event_match_t), hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(out.match_spec.data() + at, scan.match_spec_p, nm * 4, hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(out.msg.data() + at * IPCFP_CID_SLOT, msg_d.p, nm * IPCFP_CID_SLOT, hipMemcpyDeviceToHost, ctx->stream));
+        IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));  // (the chunk's device buffers go back to the pool)
+        for (size_t k = at; k < at + nm; ++k) {
+            out.match_spec[k] += uint32_t(first);
+            if (out.matches[k].exec_index >= ex.exec_len) out.spec_oor[out.match_spec[k]] = 1;  // "Missing message at index" (:244-246)
+        }
+    }
+    std::vector<CidKey> base;
+    DevBuf<CidKey> base_d;
+    rc = event_gen_mark_base(ctx, w, touched, tc, wide, order.missing_d, base, base_d);
+    if (rc) return rc;
+    std::vector<uint32_t> bits(words + 2);
+    IPCFP_HIP(ctx, hipMemcpyAsync(bits.data(), touched.p, size_t(words + 2) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    out.missing_base = bits[words + 1] != 0;
+    for (uint32_t wd = 0; wd < words; ++wd)
+        for (uint32_t m = bits[wd]; m; m &= m - 1) out.block_ids.push_back(wd * 32 + uint32_t(__builtin_ctz(m)));
+    out.common_status = IPCFP_ST_TRUE;
     return IPCFP_OK;
 }
 
@@ -552,36 +669,53 @@ int ipcfp_generate_proof_bundle(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint
         all_ids.assign(ids.begin(), ids.begin() + nb);
     }
     // ---- event specs (generator.rs:59-80) ----
+    // One pass for all of them: one execution order, one recorder, one scan per IPCFP_MAX_SCAN_SPECS specs
+    // (generate_bundle_events).  The reference stops at the first spec whose generate_event_proof fails: the specs are
+    // judged in its order afterwards, from what the pass found.
     uint64_t np = 0;
-    for (uint64_t j = 0; j < n_events; ++j) {
-        const ipcfp_event_proof_spec_t& sp = event_specs[j];
-        ipcfp_event_filter_t filter;
-        int rc = ipcfp_create_event_filter(ctx, sp.event_signature ? sp.event_signature : "", sp.topic_1 ? sp.topic_1 : "", &filter);
-        if (rc) return rc;
-        // size, then fill
-        ipcfp_status_t st = IPCFP_ST_ERR;
-        uint64_t n_p = 0, n_b = 0;
-        rc = ipcfp_generate_event_proofs(ctx, w, parent_cids40, n_parents, child_cid40, &filter, sp.has_actor_id_filter ? 1 : 0,
-                                         sp.actor_id_filter, &st, nullptr, nullptr, 0, &n_p, nullptr, nullptr, 0, &n_b);
-        if (rc) return rc;
-        event_status[j] = st;
-        if (st != IPCFP_ST_TRUE) {
-            *first_error = n_storage + j;
-            return IPCFP_OK;  // `generate_event_proof(..).await?` (generator.rs:65-74)
+    if (n_events) {
+        std::vector<ipcfp_event_filter_t> filters(n_events);
+        std::vector<uint8_t> has_actor(n_events);
+        std::vector<uint64_t> actors(n_events);
+        uint64_t n_ok = 0;  // specs whose filter could be made: a failure there is returned when the reference would reach it
+        int rc_filter = IPCFP_OK;
+        for (; n_ok < n_events; ++n_ok) {
+            const ipcfp_event_proof_spec_t& sp = event_specs[n_ok];
+            rc_filter = ipcfp_create_event_filter(ctx, sp.event_signature ? sp.event_signature : "", sp.topic_1 ? sp.topic_1 : "", &filters[n_ok]);
+            if (rc_filter) break;
+            has_actor[n_ok] = sp.has_actor_id_filter ? 1 : 0;
+            actors[n_ok] = sp.actor_id_filter;
         }
-        std::vector<ipcfp_event_match_t> m(n_p ? n_p : 1);
-        std::vector<uint8_t> mc((n_p ? n_p : 1) * IPCFP_CID_SLOT);
-        std::vector<uint32_t> ids(n_b ? n_b : 1);
-        rc = ipcfp_generate_event_proofs(ctx, w, parent_cids40, n_parents, child_cid40, &filter, sp.has_actor_id_filter ? 1 : 0,
-                                         sp.actor_id_filter, &st, m.data(), mc.data(), n_p, &n_p, ids.data(), nullptr, n_b, &n_b);
+        if (n_ok == 0) return rc_filter;
+        BundleEvents ev;
+        int rc = generate_bundle_events(ctx, w, parent_cids40, n_parents, child_cid40, filters.data(), has_actor.data(), actors.data(), n_ok, ev);
         if (rc) return rc;
-        for (uint64_t k = 0; k < n_p; ++k, ++np) {
-            if (np >= cap_proofs) continue;
-            if (matches) matches[np] = m[k];
-            if (message_cids40) std::memcpy(message_cids40 + np * IPCFP_CID_SLOT, mc.data() + k * IPCFP_CID_SLOT, IPCFP_CID_SLOT);
-            if (match_spec) match_spec[np] = uint32_t(j);
+        for (uint64_t j = 0; j < n_ok; ++j) {  // `generate_event_proof(..).await?` (generator.rs:65-74), spec by spec
+            ipcfp_status_t st = IPCFP_ST_TRUE;
+            if (ev.common_status != IPCFP_ST_TRUE) st = ipcfp_status_t(ev.common_status);
+            else if (ev.spec_oor[j]) st = IPCFP_ST_ERR;                      // "Missing message at index" precedes materialisation
+            else if (ev.missing_base) st = IPCFP_ST_ERR_MISSING_BLOCK;
+            event_status[j] = st;
+            if (st != IPCFP_ST_TRUE) {
+                *first_error = n_storage + j;
+                return IPCFP_OK;
+            }
         }
-        all_ids.insert(all_ids.end(), ids.begin(), ids.begin() + n_b);
+        if (rc_filter) return rc_filter;
+        // the reference's spec-major proof order: a stable counting partition of the scan's records by spec
+        std::vector<uint64_t> start(n_events + 1, 0);
+        for (uint32_t s : ev.match_spec) ++start[s + 1];
+        for (uint64_t j = 0; j < n_events; ++j) start[j + 1] += start[j];
+        for (size_t k = 0; k < ev.matches.size(); ++k) {
+            const uint32_t j = ev.match_spec[k];
+            const uint64_t at = start[j]++;
+            if (at >= cap_proofs) continue;
+            if (matches) matches[at] = ev.matches[k];
+            if (message_cids40) std::memcpy(message_cids40 + at * IPCFP_CID_SLOT, ev.msg.data() + k * IPCFP_CID_SLOT, IPCFP_CID_SLOT);
+            if (match_spec) match_spec[at] = j;
+        }
+        np = ev.matches.size();
+        all_ids.insert(all_ids.end(), ev.block_ids.begin(), ev.block_ids.end());
     }
     *n_proofs = np;
     // ---- the union in `Cid: Ord` order, each block once (generator.rs:84-88) ----

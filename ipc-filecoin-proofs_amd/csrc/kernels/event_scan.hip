@@ -548,6 +548,58 @@ struct ScanTailCtl {
 };
 constexpr uint32_t kScanTile = 1024;
 
+// The look-back of one tile, run by the tile's wave 0 (all 64 lanes): publishes the tile's aggregate, sums the predecessors'
+// published words into *s_prefix (LDS), publishes the inclusive prefix, and the last tile in ticket order leaves the
+// total.  One text for both tail kernels (k_scan_tail_fused here, k_scan_tail_multi in event_scan_multi.inc).
+__device__ __forceinline__ void scan_tail_lookback(const ScanTailCtl& ctl, uint32_t tile, uint32_t n_tiles, uint64_t tile_total,
+                                                   uint64_t* s_prefix) {
+    const unsigned long long tag = ctl.epoch << 34;
+    const uint32_t lane = threadIdx.x;
+    if (lane == 0)
+        __hip_atomic_store(ctl.state + tile, tag | ((tile == 0 ? 2ull : 1ull) << 32) | (tile_total & 0xffffffffull),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint64_t prefix = 0;
+    int32_t hi = int32_t(tile) - 1;  // the nearest predecessor not yet accounted for
+    while (hi >= 0) {
+        const int32_t j = hi - int32_t(lane);
+        unsigned long long v = 0;
+        bool ready = true;
+        if (j >= 0) {
+            v = __hip_atomic_load(ctl.state + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ready = (v >> 34) == ctl.epoch && ((v >> 32) & 3ull) != 0ull;
+        }
+        // the window [hi - 63, hi] can be used up to its first not-yet-published word (from hi downwards)
+        const uint64_t not_ready = __ballot(!ready);
+        const uint32_t usable = not_ready ? uint32_t(__builtin_ctzll(not_ready)) : 64u;  // lanes 0 .. usable-1
+        const uint64_t is_prefix = __ballot(ready && j >= 0 && ((v >> 32) & 3ull) == 2ull);
+        const uint64_t in_use = usable >= 64u ? ~0ull : ((1ull << usable) - 1ull);
+        const uint64_t pfx_in = is_prefix & in_use;
+        const uint32_t stop = pfx_in ? uint32_t(__builtin_ctzll(pfx_in)) : 64u;  // first inclusive prefix met
+        const uint32_t take = stop < 64u ? stop + 1u : usable;                   // lanes 0 .. take-1 contribute
+        uint64_t mine = (lane < take && j >= 0) ? (v & 0xffffffffull) : 0ull;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+        prefix += mine;
+        if (stop < 64u) break;
+        hi -= int32_t(take);
+        if (take == 0) __builtin_amdgcn_s_sleep(1);
+    }
+    if (lane == 0) {
+        if (tile != 0)
+            __hip_atomic_store(ctl.state + tile, tag | (2ull << 32) | ((prefix + tile_total) & 0xffffffffull), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        *s_prefix = prefix;
+        // (an atomic exchange that RETURNS has been performed at the coherence point before this lane goes on to the
+        // completion counter below — no fence, which on this chip is a write-back of the whole L2.  The empty asm
+        // consumes the returned value: with the result discarded the compiler may emit the no-return form, which
+        // orders nothing against the later read-modify-write of another address — ADVICE r4)
+        if (tile == n_tiles - 1) {
+            const unsigned long long before = atomicExch(ctl.total, (unsigned long long)(prefix + tile_total));
+            asm volatile("" ::"v"(before));
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_scan_tail_fused(WitnessView w, const LeafRef* __restrict__ receipts, uint32_t n,
                                                          uint64_t dense_first, ScanParams sp, const ReceiptRec* __restrict__ rrecs,
                                                          const EventRec* __restrict__ erecs, const uint32_t* __restrict__ counts,
@@ -571,54 +623,8 @@ __global__ __launch_bounds__(256) void k_scan_tail_fused(WitnessView w, const Le
     }
     uint64_t tile_total;
     const uint64_t ex = block_exclusive_scan(s, smem, &tile_total);
-    const unsigned long long tag = ctl.epoch << 34;
     // ---- publish, look back (wave 0) ----
-    if (threadIdx.x < 64) {
-        const uint32_t lane = threadIdx.x;
-        if (lane == 0)
-            __hip_atomic_store(ctl.state + tile, tag | ((tile == 0 ? 2ull : 1ull) << 32) | (tile_total & 0xffffffffull),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        uint64_t prefix = 0;
-        int32_t hi = int32_t(tile) - 1;  // the nearest predecessor not yet accounted for
-        while (hi >= 0) {
-            const int32_t j = hi - int32_t(lane);
-            unsigned long long v = 0;
-            bool ready = true;
-            if (j >= 0) {
-                v = __hip_atomic_load(ctl.state + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                ready = (v >> 34) == ctl.epoch && ((v >> 32) & 3ull) != 0ull;
-            }
-            // the window [hi - 63, hi] can be used up to its first not-yet-published word (from hi downwards)
-            const uint64_t not_ready = __ballot(!ready);
-            const uint32_t usable = not_ready ? uint32_t(__builtin_ctzll(not_ready)) : 64u;  // lanes 0 .. usable-1
-            const uint64_t is_prefix = __ballot(ready && j >= 0 && ((v >> 32) & 3ull) == 2ull);
-            const uint64_t in_use = usable >= 64u ? ~0ull : ((1ull << usable) - 1ull);
-            const uint64_t pfx_in = is_prefix & in_use;
-            const uint32_t stop = pfx_in ? uint32_t(__builtin_ctzll(pfx_in)) : 64u;  // first inclusive prefix met
-            const uint32_t take = stop < 64u ? stop + 1u : usable;                   // lanes 0 .. take-1 contribute
-            uint64_t mine = (lane < take && j >= 0) ? (v & 0xffffffffull) : 0ull;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
-            prefix += mine;
-            if (stop < 64u) break;
-            hi -= int32_t(take);
-            if (take == 0) __builtin_amdgcn_s_sleep(1);
-        }
-        if (lane == 0) {
-            if (tile != 0)
-                __hip_atomic_store(ctl.state + tile, tag | (2ull << 32) | ((prefix + tile_total) & 0xffffffffull), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-            s_prefix = prefix;
-            // (an atomic exchange that RETURNS has been performed at the coherence point before this lane goes on to the
-            // completion counter below — no fence, which on this chip is a write-back of the whole L2.  The empty asm
-            // consumes the returned value: with the result discarded the compiler may emit the no-return form, which
-            // orders nothing against the later read-modify-write of another address — ADVICE r4)
-            if (tile == n_tiles - 1) {
-                const unsigned long long before = atomicExch(ctl.total, (unsigned long long)(prefix + tile_total));
-                asm volatile("" ::"v"(before));
-            }
-        }
-    }
+    if (threadIdx.x < 64) scan_tail_lookback(ctl, tile, n_tiles, tile_total, &s_prefix);
     __syncthreads();
     // ---- the map, the offsets, the matches of this tile ----
     uint64_t o = s_prefix + ex;
@@ -788,3 +794,6 @@ int launch_scan_pass2(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& receip
 }
 
 }  // namespace ipcfp
+
+// K6 for a set of specs: the kernels of ipcfp_scan_events_multi, over the walkers above
+#include "event_scan_multi.inc"

@@ -205,6 +205,25 @@ int launch_scan_tail_fused(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* 
 int launch_count_from_table(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n,
                             const ipcfp_event_filter_t& filter, int has_actor, uint64_t actor, const EventTableView& table,
                             uint32_t* counts_d, unsigned long long* err_d);
+// --- event_scan_multi.inc (part of event_scan.hip) --- the two passes for a SET of specs (filter_set.h FsView)
+struct FsView;
+// PASS 1: counts_d[t] = matches of receipt t over all specs; table (nullable): the event table, else every receipt is walked
+int launch_count_multi(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n, const FsView& fs,
+                       const EventTableView* table, uint32_t* counts_d, unsigned long long* err_d, unsigned long long* ovf_d);
+// the tail of the table route in one launch, as launch_scan_tail_fused (same scratch, same mailbox words; [5] = *ovf_d).
+// *ovf_d (zero before PASS 1) is raised when a receipt's count or the total does not fit 32 bits
+int launch_scan_tail_multi(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n, uint64_t dense_first,
+                           const FsView& fs, const EventTableView& table, const uint32_t* counts_d, uint32_t* offsets_d, void* matches_d,
+                           uint32_t* match_spec_d, uint64_t matches_cap, uint8_t* has_match_d, uint64_t has_cap, uint64_t has_base,
+                           unsigned long long* spec_counts_d, unsigned long long* scratch_d, unsigned long long epoch,
+                           const unsigned long long* err_d, unsigned long long* ovf_d, unsigned long long* mailbox_dev,
+                           unsigned long long seq);
+// PASS 2: the any-spec map, matches_d / match_spec_d (nullable together) at offsets_d, spec_counts_d[n_specs] += per-spec totals.
+// tail_done: launch_scan_tail_multi has served the tabulated receipts — only the receipts the table leaves to the walk
+int launch_fill_multi(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& receipts_root, const LeafRef* receipts_d, uint32_t n,
+                      const FsView& fs, const uint32_t* counts_d, const uint32_t* offsets_d, void* matches_d, uint32_t* match_spec_d,
+                      uint64_t matches_cap, uint8_t* has_match_d, uint64_t has_cap, uint64_t has_base,
+                      unsigned long long* spec_counts_d, const EventTableView* table, bool tail_done);
 
 // --- base64.hip ---
 int launch_base64_decode(ipcfp_ctx* ctx, const uint8_t* text_d, const void* spans_d, uint32_t n_blocks, uint32_t n_units,
