@@ -57,6 +57,7 @@ pub const IPCFP_ABI_VERSION: c_int = 3;
 pub const IPCFP_SCAN_PHASE_RECEIPTS: u32 = 1;
 pub const IPCFP_SCAN_PHASE_EVENTS: u32 = 2;
 pub const IPCFP_MAX_SCAN_SPECS: usize = 1024;
+pub const IPCFP_MAX_SCAN_TIPSETS: usize = 4096;
 pub const IPCFP_ST_TRUE: u8 = 1;
 pub const IPCFP_ST_FALSE_FILTER: u8 = 17;
 /// `ipcfp_check_event_fn` of the header: the host predicate of ipcfp_verify_event_proofs_with
@@ -598,6 +599,51 @@ impl Witness<'_> {
             if st != IPCFP_ST_TRUE { return Err(anyhow!("find_matching_events failed with status {st}")); }
         }
         Ok((matches, match_spec, counts))
+    }
+
+    /// `scan_events_multi` for a CHAIN of tipsets in one pass (`ipcfp_scan_events_tipsets`, at most `IPCFP_MAX_SCAN_TIPSETS`
+    /// receipts roots in chain order): per tipset `Ok((records, spec of each record))` — what `scan_events_multi` returns for
+    /// that root, with `exec_index` the index within its own tipset — or `Err(status)` when its scan is an Err, which
+    /// changes nothing about the other tipsets.  The last element: the per-spec totals over the sound tipsets.
+    /// Costs TWO passes over the chain when there are matches (a sizing call, then the records), one when there are none.
+    #[allow(clippy::type_complexity)]
+    pub fn scan_events_tipsets(&self, receipts_roots: &[Cid], specs: &[(ipcfp_event_filter_t, Option<u64>)])
+                               -> Result<(Vec<std::result::Result<(Vec<ipcfp_event_match_t>, Vec<u32>), u8>>, Vec<u64>)> {
+        if specs.is_empty() || specs.len() > IPCFP_MAX_SCAN_SPECS { return Err(anyhow!("scan_events_tipsets takes 1 to {IPCFP_MAX_SCAN_SPECS} specs")); }
+        if receipts_roots.is_empty() || receipts_roots.len() > IPCFP_MAX_SCAN_TIPSETS { return Err(anyhow!("scan_events_tipsets takes 1 to {IPCFP_MAX_SCAN_TIPSETS} tipsets")); }
+        let mut roots = Vec::with_capacity(receipts_roots.len() * 40);
+        for c in receipts_roots { roots.extend_from_slice(&cid_slot(c)?); }
+        let filters: Vec<ipcfp_event_filter_t> = specs.iter().map(|s| s.0).collect();
+        let has: Vec<u8> = specs.iter().map(|s| s.1.is_some() as u8).collect();
+        let actors: Vec<u64> = specs.iter().map(|s| s.1.unwrap_or(0)).collect();
+        let (t, n) = (receipts_roots.len(), specs.len() as u32);
+        let mut st = vec![0u8; t];
+        let mut moff = vec![0u64; t + 1];
+        let (mut nr, mut nm) = (0u64, 0u64);
+        let mut counts = vec![0u64; specs.len()];
+        let mut matches: Vec<ipcfp_event_match_t> = Vec::new();
+        let mut match_spec: Vec<u32> = Vec::new();
+        for pass in 0..2 {  // the sizing call, then the records
+            let cap = matches.len() as u64;
+            let rc = unsafe { ipcfp_scan_events_tipsets(self.eng.ctx, self.raw(), roots.as_ptr(), t as u32, filters.as_ptr(), has.as_ptr(), actors.as_ptr(), n,
+                                                        st.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), moff.as_mut_ptr(),
+                                                        std::ptr::null_mut(), 0, &mut nr,
+                                                        if cap > 0 { matches.as_mut_ptr() } else { std::ptr::null_mut() },
+                                                        if cap > 0 { match_spec.as_mut_ptr() } else { std::ptr::null_mut() }, cap, &mut nm,
+                                                        counts.as_mut_ptr(), std::ptr::null_mut()) };
+            if rc != 0 { return Err(self.eng.err("ipcfp_scan_events_tipsets", rc)); }
+            if pass == 1 || nm == 0 { break; }
+            matches = vec![unsafe { std::mem::zeroed::<ipcfp_event_match_t>() }; nm as usize];
+            match_spec = vec![0u32; nm as usize];
+        }
+        if (nm as usize) != matches.len() { return Err(anyhow!("scan_events_tipsets: the witness changed between the two calls")); }
+        let mut out = Vec::with_capacity(t);
+        for k in 0..t {
+            if st[k] != IPCFP_ST_TRUE { out.push(Err(st[k])); continue; }
+            let (a, b) = (moff[k] as usize, moff[k + 1] as usize);
+            out.push(Ok((matches[a..b].to_vec(), match_spec[a..b].to_vec())));
+        }
+        Ok((out, counts))
     }
 
     /// `generate_event_proof` for one filter (src/proofs/events/generator.rs:75-178): the `EventProof`s of

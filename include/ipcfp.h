@@ -191,7 +191,8 @@ enum {
     IPCFP_K_SCAN_MULTI_COUNT = 22, /* ipcfp_scan_events_multi*: PASS 1 for a set of specs (records probed against the filter set) */
     IPCFP_K_SCAN_MULTI_FILL = 23,  /* … PASS 2: the has-map, matches + match_spec, per-spec counts */
     IPCFP_K_SCAN_MULTI_TAIL = 24,  /* … the table route's tail in one launch: look-back prefix sum, map, fill, counts, mailbox */
-    IPCFP_K_COUNT = 25
+    IPCFP_K_SCAN_TIPSETS = 25,     /* ipcfp_scan_events_tipsets*: tipset boundaries, PASS 1 / PASS 2 over the leaves of a chain */
+    IPCFP_K_COUNT = 26
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -422,6 +423,49 @@ int ipcfp_scan_events_multi_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const u
                                    uint32_t n_specs, ipcfp_status_t* status_out, void* receipt_has_match_d,
                                    uint64_t cap_receipts, uint64_t* n_receipts, void* matches_d, void* match_spec_d,
                                    uint64_t cap_matches, uint64_t* n_matches, void* spec_counts_d, void* summary_d);
+
+/* ipcfp_scan_events_multi for a CHAIN of tipsets in one pass: receipts_roots40 holds n_tipsets 40-byte slots in chain order,
+ * and the call answers exactly what n_tipsets calls of ipcfp_scan_events_multi would, one per root, with the same specs on
+ * the same witness, laid end to end.  The receipts trees are enumerated together and the two passes run once over all
+ * their receipts, so the fixed cost of a call is paid once for the chain.
+ *   tipset_status[t], tipset_phase[t]   what call t returns and what ipcfp_witness_last_scan_phase says after it (the
+ *                      phase is 0 with status TRUE; tipset_phase is nullable).  The call itself returns IPCFP_OK whatever
+ *                      the tipsets' statuses; afterwards ipcfp_witness_last_scan_phase is the phase of the LOWEST failing
+ *                      tipset, 0 when none fails.
+ *   tipset_receipt_off, tipset_match_off   (nullable) n_tipsets + 1 offsets each, never truncated: the map of tipset t is
+ *                      receipt_has_match[receipt_off[t] .. receipt_off[t + 1]) with byte r for receipt index r, its records are
+ *                      matches / match_spec in [match_off[t], match_off[t + 1]), in the order of ipcfp_scan_events_multi, with
+ *                      exec_index the index within its own tipset.
+ *   A tipset whose scan is an Err contributes NOTHING — no map byte, no record, nothing in spec_counts or touched_bits,
+ *   and an empty range in both offset arrays — and changes nothing about any other tipset.  The same root given twice is
+ *   two tipsets with two equal answers.
+ *   *n_receipts, *n_matches   the totals over all tipsets (off[n_tipsets]), whatever the capacities
+ *   cap_receipts, cap_matches cut the CONCATENATED map and record list to a prefix (cap_matches == 0 or matches == NULL: a
+ *                      sizing call); nothing is written behind the prefix
+ *   spec_counts        (nullable) n_specs totals over the sound tipsets; touched_bits (nullable) the OR of the single calls'
+ * IPCFP_E_INVALID: n_tipsets == 0, n_specs == 0, a null mandatory pointer, a has_actor[j] without actors, or a witness with a
+ * receipt range set (a shard is a cut of ONE tipset).  IPCFP_E_UNSUPPORTED: n_tipsets > IPCFP_MAX_SCAN_TIPSETS, n_specs >
+ * IPCFP_MAX_SCAN_SPECS, 2^31 - 1 or more receipts over all tipsets, 2^32 - 1 or more matches over all tipsets and specs.
+ * The call neither reads nor fills the witness's per-root caches (enumerations, event tables), the context's scan hint or
+ * the block table's filter: every single-tipset call before and after answers as it would have without it.             */
+#define IPCFP_MAX_SCAN_TIPSETS 4096 /* a day of 30-second epochs is 2880; the enumerator's error word orders 2^16 roots */
+int ipcfp_scan_events_tipsets(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* receipts_roots40, uint32_t n_tipsets,
+                              const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                              uint32_t n_specs, ipcfp_status_t* tipset_status, uint8_t* tipset_phase,
+                              uint64_t* tipset_receipt_off, uint64_t* tipset_match_off, uint8_t* receipt_has_match,
+                              uint64_t cap_receipts, uint64_t* n_receipts, ipcfp_event_match_t* matches, uint32_t* match_spec,
+                              uint64_t cap_matches, uint64_t* n_matches, uint64_t* spec_counts, uint32_t* touched_bits);
+/* … with DEVICE outputs: receipt_has_match_d (cap_receipts bytes), matches_d (cap_matches ipcfp_event_match_t), match_spec_d
+ * (cap_matches uint32), spec_counts_d (n_specs uint64) and tipset_receipt_off_d / tipset_match_off_d (n_tipsets + 1 uint64 each)
+ * are HBM buffers of the caller (nullable); the per-tipset statuses, phases, offsets and the two totals also come back to
+ * the host.  No recorder.                                                                                               */
+int ipcfp_scan_events_tipsets_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* receipts_roots40, uint32_t n_tipsets,
+                                     const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                                     uint32_t n_specs, ipcfp_status_t* tipset_status, uint8_t* tipset_phase,
+                                     uint64_t* tipset_receipt_off, uint64_t* tipset_match_off, void* tipset_receipt_off_d,
+                                     void* tipset_match_off_d, void* receipt_has_match_d, uint64_t cap_receipts,
+                                     uint64_t* n_receipts, void* matches_d, void* match_spec_d, uint64_t cap_matches,
+                                     uint64_t* n_matches, void* spec_counts_d);
 
 /* ---- proof claims (string form, exactly the reference's structs) ----------
  * CIDs and hex values are NUL-terminated strings, as in the reference's serde

@@ -16,6 +16,7 @@ __all__ = [
     "SCAN_PHASE_RECEIPTS",
     "SCAN_PHASE_EVENTS",
     "MAX_SCAN_SPECS",
+    "MAX_SCAN_TIPSETS",
     "merge_scan_status",
     "host_register",
     "ingest_buffer",
@@ -106,9 +107,11 @@ KERNEL_IDS = {
     "scan_multi_count": 22,
     "scan_multi_fill": 23,
     "scan_multi_tail": 24,
+    "scan_tipsets": 25,
 }
 
 MAX_SCAN_SPECS = 1024
+MAX_SCAN_TIPSETS = 4096
 
 
 class ST:
@@ -423,6 +426,8 @@ def load_library() -> C.CDLL:
         "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
         "ipcfp_scan_events_multi": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
         "ipcfp_scan_events_multi_device": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
+        "ipcfp_scan_events_tipsets": (i32, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
+        "ipcfp_scan_events_tipsets_device": (i32, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -1644,6 +1649,84 @@ class Witness:
                                                                 C.byref(nm), spec_counts_ptr or None, summary_ptr or None),
                         "scan_events_multi_device")
         return int(st[0]), int(nr.value), int(nm.value)
+
+    def scan_events_tipsets(self, receipts_roots, specs, want_touched=True, cap_matches=None, cap_receipts=None):
+        """The scan of a CHAIN of tipsets for a set of specs in one pass (ipcfp_scan_events_tipsets): what
+        [scan_events_multi(root, specs) for root in receipts_roots] answers, laid end to end.  → a dict:
+          status u8[T], phase u8[T]       per tipset (phase 0 with status 1)
+          receipt_off, match_off u64[T+1] never truncated; n_receipts, n_matches: their last entries
+          has_match u8, matches structured, match_spec u32   the concatenated arrays, cut to cap_receipts / cap_matches
+          spec_counts u64[n_specs], touched (block ids, None without want_touched)
+          maps, records, record_specs     per tipset, split by the offsets (what the capacities cut away is missing);
+                                          a failing tipset's are empty
+        The ABI call is made TWICE — a sizing call, then the call that takes the outputs — and each is a whole pass (an
+        enumeration and both passes over the chain); when the sizing call shows nothing to fetch (no map byte and no record
+        inside the capacities, no recorder asked for) the second call is not made.  A caller that knows its capacities
+        uses scan_events_tipsets_device, one pass."""
+        roots = cid_slots(list(receipts_roots)).copy() if len(receipts_roots) else np.zeros((0, CID_SLOT), dtype=np.uint8)
+        filt, has_a, actors = self._scan_specs(specs)
+        T, n = len(receipts_roots), len(specs)
+        st = np.zeros(max(T, 1), dtype=np.uint8)
+        ph = np.zeros(max(T, 1), dtype=np.uint8)
+        roff = np.zeros(T + 1, dtype=np.uint64)
+        moff = np.zeros(T + 1, dtype=np.uint64)
+        nr, nm = C.c_uint64(), C.c_uint64()
+        counts = np.zeros(max(n, 1), dtype=np.uint64)
+
+        def call(has, m, ms, touched):
+            self.eng._check(self.lib.ipcfp_scan_events_tipsets(self.eng.h, self.h, _p(roots), T, _p(filt), _p(has_a), _p(actors), n,
+                                                               _p(st), _p(ph), _p(roff), _p(moff),
+                                                               _p(has), 0 if has is None else len(has), C.byref(nr),
+                                                               _p(m), _p(ms), 0 if m is None else len(m), C.byref(nm),
+                                                               _p(counts), _p(touched)), "scan_events_tipsets")
+
+        call(None, None, None, None)  # the sizing call
+        total_r, total_m = int(nr.value), int(nm.value)
+        take_r = total_r if cap_receipts is None else min(total_r, int(cap_receipts))
+        take_m = total_m if cap_matches is None else min(total_m, int(cap_matches))
+        has = np.zeros(take_r, dtype=np.uint8) if take_r else None
+        m = np.zeros(take_m, dtype=MATCH_DTYPE) if take_m else None
+        ms = np.zeros(take_m, dtype=np.uint32) if take_m else None
+        touched = np.zeros(max((self.n + 31) // 32, 1), dtype=np.uint32) if want_touched else None
+        if take_r or take_m or want_touched:  # (else the sizing call has answered: statuses, offsets, totals, spec_counts)
+            call(has, m, ms, touched)
+        has = np.zeros(0, dtype=np.uint8) if has is None else has
+        m = np.zeros(0, dtype=MATCH_DTYPE) if m is None else m
+        ms = np.zeros(0, dtype=np.uint32) if ms is None else ms
+        ids = None
+        if want_touched:
+            ids = np.nonzero(np.unpackbits(touched.view(np.uint8), bitorder="little")[: self.n])[0]
+        r, o = [int(v) for v in roff], [int(v) for v in moff]
+        return {
+            "status": st[:T].copy(), "phase": ph[:T].copy(), "receipt_off": roff, "match_off": moff,
+            "n_receipts": int(nr.value), "n_matches": int(nm.value), "has_match": has, "matches": m, "match_spec": ms,
+            "spec_counts": counts[:n].copy(), "touched": ids,
+            "maps": [has[min(r[t], take_r):min(r[t + 1], take_r)] for t in range(T)],
+            "records": [m[min(o[t], take_m):min(o[t + 1], take_m)] for t in range(T)],
+            "record_specs": [ms[min(o[t], take_m):min(o[t + 1], take_m)] for t in range(T)],
+        }
+
+    def scan_events_tipsets_device(self, receipts_roots, specs, has_ptr: int = 0, cap_receipts: int = 0, matches_ptr: int = 0,
+                                   match_spec_ptr: int = 0, cap_matches: int = 0, spec_counts_ptr: int = 0,
+                                   receipt_off_ptr: int = 0, match_off_ptr: int = 0):
+        """ipcfp_scan_events_tipsets_device: the concatenated map, the records, match_spec, the per-spec counts and (optionally)
+        the two offset arrays stay in HBM (pointers of the caller, 0: not wanted).
+        → (status u8[T], phase u8[T], receipt_off u64[T+1], match_off u64[T+1], n_receipts, n_matches)"""
+        roots = cid_slots(list(receipts_roots)).copy() if len(receipts_roots) else np.zeros((0, CID_SLOT), dtype=np.uint8)
+        filt, has_a, actors = self._scan_specs(specs)
+        T = len(receipts_roots)
+        st = np.zeros(max(T, 1), dtype=np.uint8)
+        ph = np.zeros(max(T, 1), dtype=np.uint8)
+        roff = np.zeros(T + 1, dtype=np.uint64)
+        moff = np.zeros(T + 1, dtype=np.uint64)
+        nr, nm = C.c_uint64(), C.c_uint64()
+        self.eng._check(self.lib.ipcfp_scan_events_tipsets_device(self.eng.h, self.h, _p(roots), T, _p(filt), _p(has_a), _p(actors),
+                                                                  len(specs), _p(st), _p(ph), _p(roff), _p(moff),
+                                                                  receipt_off_ptr or None, match_off_ptr or None,
+                                                                  has_ptr or None, int(cap_receipts), C.byref(nr),
+                                                                  matches_ptr or None, match_spec_ptr or None, int(cap_matches),
+                                                                  C.byref(nm), spec_counts_ptr or None), "scan_events_tipsets_device")
+        return st[:T].copy(), ph[:T].copy(), roff, moff, int(nr.value), int(nm.value)
 
     # -- generator side -------------------------------------------------------------------------
     def generate_event_proofs(self, parent_cids, child_cid: bytes, topic0: bytes, topic1: bytes, actor=None):

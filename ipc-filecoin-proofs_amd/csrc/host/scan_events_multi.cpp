@@ -22,8 +22,8 @@ using namespace ipcfp;
 namespace ipcfp {
 
 // the set, built on the host and uploaded with ONE copy: [slots | groups | members]
-static int upload_filter_set(ipcfp_ctx* ctx, const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
-                             uint32_t n_specs, std::vector<uint8_t>& host, DevBuf<uint8_t>& dev, FsView& view) {
+int upload_filter_set(ipcfp_ctx* ctx, const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                      uint32_t n_specs, std::vector<uint8_t>& host, DevBuf<uint8_t>& dev, FsView& view) {
     const uint32_t n_slots = fs_slots_for(n_specs);
     const size_t slots_b = size_t(n_slots) * sizeof(FsSlot), groups_b = size_t(n_specs) * sizeof(FsGroup),
                  members_b = size_t(n_specs) * sizeof(FsMember);

@@ -1,5 +1,7 @@
 // csrc/host/scan_events_multi.h — the scan for a set of specs (host/scan_events_multi.cpp), for the host code that builds on it.
 #pragma once
+#include <vector>
+
 #include "../common.h"
 
 namespace ipcfp {
@@ -29,5 +31,11 @@ struct MultiScanResult {
 int scan_events_multi_device(ipcfp_ctx* ctx, ipcfp_witness* w, const CidKey& root, const ipcfp_event_filter_t* filters,
                              const uint8_t* has_actor, const uint64_t* actors, uint32_t n_specs, uint32_t* touched_d,
                              MultiScanResult& out, uint64_t cap_matches);
+
+// the filter set of a call (kernels/filter_set.h), built in `host` and queued for upload with one copy: `host` must outlive
+// the copy, i.e. the caller drains the stream before it goes away
+struct FsView;
+int upload_filter_set(ipcfp_ctx* ctx, const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors,
+                      uint32_t n_specs, std::vector<uint8_t>& host, DevBuf<uint8_t>& dev, FsView& view);
 
 }  // namespace ipcfp

@@ -797,3 +797,5 @@ int launch_scan_pass2(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& receip
 
 // K6 for a set of specs: the kernels of ipcfp_scan_events_multi, over the walkers above
 #include "event_scan_multi.inc"
+// … and for a chain of tipsets: the kernels of ipcfp_scan_events_tipsets
+#include "event_scan_tipsets.inc"

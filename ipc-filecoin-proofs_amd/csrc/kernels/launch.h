@@ -225,6 +225,26 @@ int launch_fill_multi(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& receip
                       uint64_t matches_cap, uint8_t* has_match_d, uint64_t has_cap, uint64_t has_base,
                       unsigned long long* spec_counts_d, const EventTableView* table, bool tail_done);
 
+// --- event_scan_tipsets.inc (part of event_scan.hip) --- the two passes over the concatenated leaves of T receipts trees
+struct AmtRootSpec;
+// first_d[s] (s = 0 … n_tipsets): position of the first leaf with seq >= s; n == 0 is served (every entry 0)
+int launch_tipset_bounds(ipcfp_ctx* ctx, const LeafRef* leaves_d, uint32_t n, uint32_t n_tipsets, uint32_t* first_d);
+// PASS 1 as launch_count_multi with one error word per tipset (err_d[n_tipsets], kNoEnumError each), then the counts of
+// every leaf of a tipset whose word is set are zeroed
+int launch_count_tipsets(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* receipts_d, uint32_t n, const FsView& fs,
+                         const EventTableView* table, uint32_t* counts_d, unsigned long long* err_d, uint32_t n_tipsets,
+                         unsigned long long* ovf_d);
+// behind launch_scan_u32: per tipset the size of its map (last index + 1) and the record offset at its first leaf
+int launch_tipset_shapes(ipcfp_ctx* ctx, const LeafRef* leaves_d, uint32_t n, const uint32_t* first_d, const uint32_t* offsets_d,
+                         const uint64_t* total_d, uint32_t n_tipsets, uint64_t* n_idx_d, uint64_t* match_start_d);
+// PASS 2 as launch_fill_multi: the map byte of a leaf at receipt_off_d[seq] + index (n_tipsets + 1 offsets; has_cap bounds the
+// concatenated map), the recorder's receipts root from roots_d[seq]
+int launch_fill_tipsets(ipcfp_ctx* ctx, const WitnessView& w, const AmtRootSpec* roots_d, const unsigned long long* err_d,
+                        const uint64_t* receipt_off_d, uint32_t n_tipsets, const LeafRef* receipts_d, uint32_t n, const FsView& fs,
+                        const uint32_t* counts_d, const uint32_t* offsets_d, void* matches_d, uint32_t* match_spec_d,
+                        uint64_t matches_cap, uint8_t* has_match_d, uint64_t has_cap, unsigned long long* spec_counts_d,
+                        const EventTableView* table);
+
 // --- base64.hip ---
 int launch_base64_decode(ipcfp_ctx* ctx, const uint8_t* text_d, const void* spans_d, uint32_t n_blocks, uint32_t n_units,
                          const uint64_t* dst_off_d, uint8_t* arena_d, unsigned long long* first_bad_d);
