@@ -58,6 +58,7 @@ pub const IPCFP_SCAN_PHASE_RECEIPTS: u32 = 1;
 pub const IPCFP_SCAN_PHASE_EVENTS: u32 = 2;
 pub const IPCFP_MAX_SCAN_SPECS: usize = 1024;
 pub const IPCFP_MAX_SCAN_TIPSETS: usize = 4096;
+pub const IPCFP_MAX_GEN_TIPSETS: usize = 4096;
 pub const IPCFP_ST_TRUE: u8 = 1;
 pub const IPCFP_ST_FALSE_FILTER: u8 = 17;
 /// `ipcfp_check_event_fn` of the header: the host predicate of ipcfp_verify_event_proofs_with
@@ -755,6 +756,19 @@ impl GeneratedStorageClaims<'_> {
         let ids = unsafe { ipcfp_generated_storage_claims_block_ids(self.raw, &mut nb) };
         if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() }
     }
+    /// Children of the chain the handle answers (`generate_storage_claims_tipsets*`); 1 for a single-child handle.
+    pub fn tipset_count(&self) -> u32 { unsafe { ipcfp_generated_storage_claims_tipset_count(self.raw) } }
+    /// Index WITHIN tipset `t` of its first failing spec: where that epoch's `generate_proof_bundle` aborts.
+    pub fn tipset_first_error(&mut self, t: u32) -> Option<u64> {
+        let v = unsafe { ipcfp_generated_storage_claims_tipset_first_error(self.raw, t) };
+        if v == u64::MAX { None } else { Some(v) }
+    }
+    /// Ids of the blocks tipset `t` alone recorded, in `Cid: Ord` order: the witness of the bundle for that epoch.
+    pub fn tipset_block_ids(&self, t: u32) -> Vec<u32> {
+        let mut nb = 0u64;
+        let ids = unsafe { ipcfp_generated_storage_claims_tipset_block_ids(self.raw, t, &mut nb) };
+        if ids.is_null() || nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() }
+    }
     /// `verify_storage_proof` of the handle's own columns against `w` (`ipcfp_verify_storage_columns_device`), status bytes
     /// written to `status_d` (device memory, one byte per spec).
     pub fn verify_columns(&self, w: &Witness<'_>, trust: Option<&ipcfp_trust_policy_t>, status_d: *mut std::ffi::c_void) -> Result<()> {
@@ -791,6 +805,40 @@ impl<'e> Witness<'e> {
         let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
         let rc = ipcfp_generate_storage_claims_device(self.eng.ctx, self.raw(), child.as_ptr(), child_epoch, actor_ids_d, slots32_d, n, &mut g);
         if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims_device", rc)); }
+        Ok(GeneratedStorageClaims { eng: self.eng, raw: g })
+    }
+
+    /// `ipcfp_generate_storage_claims_tipsets`: the same spec list posed at every `(child CID, child epoch)` of a chain (at
+    /// most `IPCFP_MAX_GEN_TIPSETS`) in one pass — `children.len() * specs.len()` claims in (tipset, spec) order.
+    pub fn generate_storage_claims_tipsets(&self, children: &[(Cid, i64)], specs: &[(u64, [u8; 32])]) -> Result<GeneratedStorageClaims<'e>> {
+        if children.is_empty() || children.len() > IPCFP_MAX_GEN_TIPSETS { return Err(anyhow!("generate_storage_claims_tipsets takes 1 to {IPCFP_MAX_GEN_TIPSETS} tipsets")); }
+        let mut cids = Vec::with_capacity(children.len() * IPCFP_CID_SLOT);
+        for c in children { cids.extend_from_slice(&cid_slot(&c.0)?); }
+        let epochs: Vec<i64> = children.iter().map(|c| c.1).collect();
+        let actors: Vec<u64> = specs.iter().map(|s| s.0).collect();
+        let mut slots = Vec::with_capacity(specs.len() * 32);
+        for s in specs { slots.extend_from_slice(&s.1); }
+        let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
+        let rc = unsafe { ipcfp_generate_storage_claims_tipsets(self.eng.ctx, self.raw(), cids.as_ptr(), epochs.as_ptr(), children.len() as u32,
+                                                                actors.as_ptr(), slots.as_ptr(), specs.len() as u64, &mut g) };
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims_tipsets", rc)); }
+        Ok(GeneratedStorageClaims { eng: self.eng, raw: g })
+    }
+
+    /// `ipcfp_generate_storage_claims_tipsets_device`: the spec list resident in HBM.
+    ///
+    /// # Safety
+    /// As `generate_storage_claims_device`, for `n_specs` entries.
+    pub unsafe fn generate_storage_claims_tipsets_device(&self, children: &[(Cid, i64)], actor_ids_d: *const std::ffi::c_void,
+                                                         slots32_d: *const std::ffi::c_void, n_specs: u64) -> Result<GeneratedStorageClaims<'e>> {
+        if children.is_empty() || children.len() > IPCFP_MAX_GEN_TIPSETS { return Err(anyhow!("generate_storage_claims_tipsets_device takes 1 to {IPCFP_MAX_GEN_TIPSETS} tipsets")); }
+        let mut cids = Vec::with_capacity(children.len() * IPCFP_CID_SLOT);
+        for c in children { cids.extend_from_slice(&cid_slot(&c.0)?); }
+        let epochs: Vec<i64> = children.iter().map(|c| c.1).collect();
+        let mut g = std::ptr::null_mut::<ipcfp_generated_storage_claims_t>();
+        let rc = ipcfp_generate_storage_claims_tipsets_device(self.eng.ctx, self.raw(), cids.as_ptr(), epochs.as_ptr(), children.len() as u32,
+                                                              actor_ids_d, slots32_d, n_specs, &mut g);
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_storage_claims_tipsets_device", rc)); }
         Ok(GeneratedStorageClaims { eng: self.eng, raw: g })
     }
 }

@@ -990,6 +990,40 @@ const uint32_t* ipcfp_generated_storage_claims_block_ids(const ipcfp_generated_s
 int ipcfp_generated_storage_claims_proofs(ipcfp_generated_storage_claims_t* g, const ipcfp_storage_proof_t** proofs,
                                           uint64_t* n, uint64_t* bad_index);
 
+/* ---- … for a CHAIN of child headers in one pass ------------------------------------------------------------------------
+ * The same n_specs (actor_id, slot) list posed at every child t of n_tipsets, with child_epochs[t] (child_cids40: n_tipsets
+ * slots of IPCFP_CID_SLOT bytes; both arrays in host memory on either form) — what a relayer that reads the same few slots
+ * at every epoch of a finality range asks.  The handle holds n = n_tipsets * n_specs claims in (tipset, spec) order and
+ * answers exactly what n_tipsets calls of ipcfp_generate_storage_claims would, laid end to end:
+ *   columns, status   [t * n_specs, (t + 1) * n_specs) are byte for byte those of call t
+ *   run table         the n_tipsets run tables concatenated, each first_claim shifted by t * n_specs; a run never crosses a
+ *                     tipset, and two neighbouring tipsets with the same child are still two sets of runs
+ *   _block_ids        the UNION of the blocks recorded over all tipsets, each once, in `Cid: Ord` order
+ *   _tipset_block_ids(t)    id for id what call t's _block_ids returns: the witness of the bundle for epoch t
+ *   _first_error      over all claims;  _tipset_first_error(t): call t's _first_error — an index WITHIN tipset t, or UINT64_MAX
+ *   a failing tipset  (child header absent or undecodable, a bad StateRoot) does not vanish: n_specs well-formed failing
+ *                     claims with the statuses, flags and zeroed fields of the single call; no other tipset changes
+ *   _copy, _proofs, _status, _run_count and the device pointers work unchanged over the whole.
+ * On a single-child handle _tipset_count is 1 and tipset 0 is the whole.
+ * IPCFP_E_INVALID: n_tipsets == 0, a null mandatory pointer, the alignment rules of the single _device form.
+ * n_specs == 0: IPCFP_OK and an empty handle that remembers its tipset count.
+ * IPCFP_E_UNSUPPORTED: n_tipsets > IPCFP_MAX_GEN_TIPSETS; n_tipsets * n_specs >= 2^32 - 1; a recorder — one bitmap row of
+ * ceil(blocks / 32) words per tipset — of more than 2^28 words (1 GiB): a caller at that size cuts the chain.
+ * Route: the node-table rule and the tuning key "hamt_table" of the single call, applied to n_tipsets * n_specs claims
+ * against the witness's block count.  After any refusal *out is NULL.                                                  */
+#define IPCFP_MAX_GEN_TIPSETS 4096
+int ipcfp_generate_storage_claims_tipsets(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cids40,
+                                          const int64_t* child_epochs, uint32_t n_tipsets, const uint64_t* actor_ids,
+                                          const uint8_t* slots32, uint64_t n_specs, ipcfp_generated_storage_claims_t** out);
+int ipcfp_generate_storage_claims_tipsets_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cids40,
+                                                 const int64_t* child_epochs, uint32_t n_tipsets, const void* actor_ids_d,
+                                                 const void* slots32_d, uint64_t n_specs,
+                                                 ipcfp_generated_storage_claims_t** out);
+uint32_t ipcfp_generated_storage_claims_tipset_count(const ipcfp_generated_storage_claims_t* g);
+uint64_t ipcfp_generated_storage_claims_tipset_first_error(ipcfp_generated_storage_claims_t* g, uint32_t t);
+const uint32_t* ipcfp_generated_storage_claims_tipset_block_ids(const ipcfp_generated_storage_claims_t* g, uint32_t t,
+                                                                uint64_t* n);
+
 /* The host inverse of ipcfp_pack_storage_proofs (no device, no context): packed claims → StorageProof structs with the
  * strings the reference writes — every CID `Cid::to_string()`, slot and value `format!("0x{}", hex::encode(..))`
  * (src/proofs/storage/generator.rs:158-178).  All or nothing; *bad_index (nullable) names the lowest offending claim.

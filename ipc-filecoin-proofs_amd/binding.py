@@ -406,6 +406,11 @@ def load_library() -> C.CDLL:
         "ipcfp_unpacked_events_destroy": (None, [vp]),
         "ipcfp_generate_storage_claims": (i32, [vp, vp, vp, C.c_int64, vp, vp, u64, C.POINTER(vp)]),
         "ipcfp_generate_storage_claims_device": (i32, [vp, vp, vp, C.c_int64, vp, vp, u64, C.POINTER(vp)]),
+        "ipcfp_generate_storage_claims_tipsets": (i32, [vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(vp)]),
+        "ipcfp_generate_storage_claims_tipsets_device": (i32, [vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(vp)]),
+        "ipcfp_generated_storage_claims_tipset_count": (C.c_uint32, [vp]),
+        "ipcfp_generated_storage_claims_tipset_first_error": (u64, [vp, C.c_uint32]),
+        "ipcfp_generated_storage_claims_tipset_block_ids": (vp, [vp, C.c_uint32, C.POINTER(u64)]),
         "ipcfp_generated_storage_claims_destroy": (None, [vp]),
         "ipcfp_generated_storage_claims_count": (u64, [vp]),
         "ipcfp_generated_storage_claims_run_count": (C.c_uint32, [vp]),
@@ -1258,6 +1263,28 @@ class GeneratedStorageClaims:
         v = int(self.lib.ipcfp_generated_storage_claims_first_error(self.h))
         return None if v == 2**64 - 1 else v
 
+    @property
+    def n_tipsets(self) -> int:
+        """Children of the chain the handle answers (generate_storage_claims_tipsets*); 1 for a single-child handle."""
+        return int(self.lib.ipcfp_generated_storage_claims_tipset_count(self.h))
+
+    def tipset_first_error(self, t: int):
+        """Index WITHIN tipset t of its first spec whose status is not 1, or None."""
+        if not 0 <= t < self.n_tipsets:
+            raise IndexError(t)
+        v = int(self.lib.ipcfp_generated_storage_claims_tipset_first_error(self.h, t))
+        return None if v == 2**64 - 1 else v
+
+    def tipset_block_ids(self, t: int) -> np.ndarray:
+        """The blocks tipset t alone recorded, in `Cid: Ord` order: what a single call for that child returns."""
+        if not 0 <= t < self.n_tipsets:
+            raise IndexError(t)
+        nb = C.c_uint64()
+        pb = self.lib.ipcfp_generated_storage_claims_tipset_block_ids(self.h, t, C.byref(nb))
+        if not nb.value:
+            return np.zeros(0, np.uint32)
+        return np.frombuffer((C.c_uint8 * (4 * nb.value)).from_address(pb), dtype=np.uint32).copy()
+
     def copy(self):
         """→ (runs record[n_runs], slot u8[n, 32], value u8[n, 32], cflags u8[n]) on the host."""
         runs = np.zeros(self.n_runs, dtype=_SRUN_DTYPE)
@@ -1807,6 +1834,37 @@ class Witness:
         self.eng._check(self.lib.ipcfp_generate_storage_claims_device(self.eng.h, self.h, _p(child), int(child_epoch),
                                                                       actor_ids_ptr or None, slots_ptr or None, int(n), C.byref(h)),
                         "generate_storage_claims_device")
+        return GeneratedStorageClaims(self.eng, h)
+
+    def generate_storage_claims_tipsets(self, child_cids, child_epochs, actor_ids, slots32) -> "GeneratedStorageClaims":
+        """The same list of n_specs (actor_id, slot) specs posed at every child of a chain (child_cids: CID bytes per tipset,
+        child_epochs: one epoch each) in one pass (ipcfp_generate_storage_claims_tipsets) → GeneratedStorageClaims over
+        n_tipsets · n_specs claims in (tipset, spec) order, with `n_tipsets`, `tipset_first_error(t)`, `tipset_block_ids(t)`."""
+        children = np.ascontiguousarray(cid_slots(list(child_cids))).reshape(-1, 40) if len(child_cids) else np.zeros((0, 40), np.uint8)
+        epochs = np.ascontiguousarray(child_epochs, dtype=np.int64)
+        if len(epochs) != len(children):
+            raise ValueError("one epoch per child")
+        ids_in = np.ascontiguousarray(actor_ids, dtype=np.uint64)
+        slots = np.ascontiguousarray(slots32, dtype=np.uint8).reshape(-1, 32)
+        n = len(ids_in)
+        h = C.c_void_p()
+        self.eng._check(self.lib.ipcfp_generate_storage_claims_tipsets(
+            self.eng.h, self.h, _p(children) if len(children) else None, _p(epochs) if len(epochs) else None, len(children),
+            _p(ids_in) if n else None, _p(slots) if n else None, n, C.byref(h)), "generate_storage_claims_tipsets")
+        return GeneratedStorageClaims(self.eng, h)
+
+    def generate_storage_claims_tipsets_device(self, child_cids, child_epochs, actor_ids_ptr: int, slots_ptr: int,
+                                               n_specs: int) -> "GeneratedStorageClaims":
+        """The same with the spec list resident in HBM: actor ids u64[n_specs], slots u8[n_specs][32] on a 16-byte boundary
+        (the children and their epochs stay host arrays)."""
+        children = np.ascontiguousarray(cid_slots(list(child_cids))).reshape(-1, 40) if len(child_cids) else np.zeros((0, 40), np.uint8)
+        epochs = np.ascontiguousarray(child_epochs, dtype=np.int64)
+        if len(epochs) != len(children):
+            raise ValueError("one epoch per child")
+        h = C.c_void_p()
+        self.eng._check(self.lib.ipcfp_generate_storage_claims_tipsets_device(
+            self.eng.h, self.h, _p(children) if len(children) else None, _p(epochs) if len(epochs) else None, len(children),
+            actor_ids_ptr or None, slots_ptr or None, int(n_specs), C.byref(h)), "generate_storage_claims_tipsets_device")
         return GeneratedStorageClaims(self.eng, h)
 
     # -- verifiers (claim arrays are ctypes arrays of the ipcfp.h structs) -------------------

@@ -764,6 +764,14 @@ struct ipcfp_generated_storage_claims {
     uint64_t first_error = ~0ull;
     std::vector<ipcfp_storage_claim_t> rows_h;
     ipcfp_unpacked_storage_t* unpacked = nullptr;
+    // a chain (ipcfp_generate_storage_claims_tipsets*): n = n_tipsets · n_specs claims in (tipset, spec) order; block_ids is
+    // the union, tipset_ids[tipset_off[t] .. tipset_off[t + 1]) tipset t's own list.  A single-child handle is a chain of
+    // one whose list IS block_ids (tipset_off stays empty).
+    uint32_t n_tipsets = 1;
+    uint64_t n_specs = 0;
+    std::vector<uint64_t> tipset_off;
+    std::vector<uint32_t> tipset_ids;
+    std::vector<uint64_t> tipset_first_error;  // with the host copy
 };
 
 namespace {
@@ -791,9 +799,120 @@ int sgen_host_copy(ipcfp_generated_storage_claims* g) {
             g->first_error = i;
             break;
         }
+    g->tipset_first_error.assign(g->n_tipsets, ~0ull);
+    for (uint32_t t = 0; t < g->n_tipsets; ++t)
+        for (uint64_t i = 0; i < g->n_specs; ++i)
+            if (g->status_h[t * g->n_specs + i] != IPCFP_ST_TRUE) {
+                g->tipset_first_error[t] = i;
+                break;
+            }
     g->have_host = true;
     return IPCFP_OK;
 }
+
+// The per-call HAMT node table and the runs of a spec list, as the single call and the chain form share them: the table is
+// the verifier's, made the way verify_storage_impl makes it (same kernels, same placement: the lane kernel on the aux
+// stream, the 32-lane outline of the long blocks on the K1 stream, the main stream discovering the runs and walking their
+// chain meanwhile).  The guards are the last members: they drain the side streams before the buffers go back to the pool.
+struct SgenPrologue {
+    static constexpr uint32_t kTableKinds = HK_ACTOR_STATE | HK_VEC_U8;
+    const bool tabled, side, side2;
+    DevBuf<HamtNodeRec> table;
+    DevBuf<uint32_t> long_list, long_count, flag, pos, run_of;
+    DevBuf<uint64_t> scratch, total_d;
+    uint64_t n_runs = 0;
+    uint32_t n_long = 0;
+    hipEvent_t outline_done = nullptr;
+    StreamDrainGuard aux_guard, k1_guard;
+
+    SgenPrologue(ipcfp_ctx* ctx, bool use_table)
+        : tabled(use_table),
+          side(use_table && ctx->stream_aux != ctx->stream && ctx->aux_event && ctx->main_event),
+          side2(side && ctx->stream_k1 != ctx->stream && ctx->stream_k1 != ctx->stream_aux),
+          aux_guard(ctx->stream_aux),
+          k1_guard(ctx->stream_k1) {}
+
+    // the table's lane kernel queued, then run discovery over the n specs: one lane per spec, the prefix sum, and the
+    // number of runs with the call's one synchronisation
+    int discover(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint64_t* actor_d, uint32_t n) {
+        int rc = IPCFP_OK;
+        if (tabled) {
+            IPCFP_HIP(ctx, table.alloc(wit->n));
+            IPCFP_HIP(ctx, long_list.alloc(wit->n));
+            IPCFP_HIP(ctx, long_count.alloc(1));
+            IPCFP_HIP(ctx, hipMemsetAsync(long_count.p, 0, 4, ctx->stream));
+            rc = launch_hamt_list_long(ctx, wit->k1_meta.p, uint32_t(wit->n), long_list.p, long_count.p);
+            if (rc) return rc;
+            if (side) {
+                IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));
+                IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
+                aux_guard.armed = true;
+                hipStream_t saved = ctx->stream;
+                ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
+                rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
+                ctx->stream = saved;
+            } else {
+                rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
+            }
+            if (rc) return rc;
+        }
+        IPCFP_HIP(ctx, flag.alloc(n));
+        IPCFP_HIP(ctx, pos.alloc(n));
+        IPCFP_HIP(ctx, run_of.alloc(n));
+        IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
+        IPCFP_HIP(ctx, total_d.alloc(1));
+        rc = launch_sgen_run_flags(ctx, actor_d, n, flag.p);
+        if (rc) return rc;
+        {
+            ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
+            rc = launch_scan_u32(ctx, flag.p, n, pos.p, total_d.p, scratch.p);
+        }
+        if (rc) return rc;
+        IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
+        if (tabled) IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
+        IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+        return IPCFP_OK;
+    }
+
+    // the long blocks' records, beside the main stream where the context has the streams for it
+    int outline(ipcfp_ctx* ctx, const WitnessView& plain) {
+        if (n_long) {
+            hipStream_t s = ctx->stream;
+            if (side2) {
+                s = ctx->stream_k1;
+                k1_guard.armed = true;
+                IPCFP_HIP(ctx, hipStreamWaitEvent(s, ctx->main_event, 0));
+            } else if (ctx->stream_aux != ctx->stream && ctx->aux_event) {
+                s = ctx->stream_aux;
+                aux_guard.armed = true;
+            }
+            int rc = launch_hamt_outline_list(ctx, s, plain, table.p, long_list.p, long_count.p, n_long);
+            if (!rc) rc = launch_hamt_node_table_rest(ctx, s, plain, long_list.p, long_count.p, n_long, kTableKinds, table.p);
+            if (rc) return rc;
+            if (s == ctx->stream_k1) {
+                if (!ctx->outline_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&ctx->outline_event, hipEventDisableTiming));
+                outline_done = ctx->outline_event;
+                IPCFP_HIP(ctx, hipEventRecord(outline_done, s));
+            }
+        }
+        if (aux_guard.armed) IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
+        return IPCFP_OK;
+    }
+
+    // run_of and every run's first_claim (runs_d: StorageRun[n_runs])
+    int heads(ipcfp_ctx* ctx, uint32_t n, void* runs_d) {
+        ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
+        return launch_storage_run_heads(ctx, flag.p, pos.p, n, run_of.p, runs_d);
+    }
+
+    // the table is whole behind this: the main stream is ordered behind the side kernels
+    int join(ipcfp_ctx* ctx) {
+        if (aux_guard.armed) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_event, 0));
+        if (outline_done) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_done, 0));
+        aux_guard.armed = k1_guard.armed = false;
+        return IPCFP_OK;
+    }
+};
 
 // The specs are in HBM (actor_d, slot_d); `own_slots` (nullable): a buffer of the call's own that already holds the slot
 // column and becomes the handle's, else the column is copied.
@@ -803,8 +922,9 @@ int generate_storage_claims_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint8
         new (std::nothrow) ipcfp_generated_storage_claims(), ipcfp_generated_storage_claims_destroy);
     if (!g) return set_error(ctx, IPCFP_E_NOMEM, "generate_storage_claims: out of memory");
     g->ctx = ctx;
-    g->n = n64;
+    g->n = g->n_specs = n64;
     if (n64 == 0) {
+        g->tipset_first_error.assign(1, ~0ull);
         g->have_host = true;
         *out = g.release();
         return IPCFP_OK;
@@ -830,98 +950,29 @@ int generate_storage_claims_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint8
     IPCFP_HIP(ctx, g->cflags_d.alloc(n64));
     IPCFP_HIP(ctx, g->status_d.alloc(n64));
     constexpr uint32_t kUndecided = 0xfdu;
-    constexpr uint32_t kTableKinds = HK_ACTOR_STATE | HK_VEC_U8;
-    DevBuf<HamtNodeRec> table;
-    DevBuf<uint32_t> long_list, long_count, flag, pos, run_of;
-    DevBuf<uint64_t> scratch, total_d;
     DevBuf<StorageRun> runs;
-    // The node table is the verifier's, made the way verify_storage_impl makes it (same kernels, same placement: the lane
-    // kernel on the aux stream, the 32-lane outline of the long blocks on the K1 stream, the main stream discovering the
-    // runs and walking their chain meanwhile); the guards drain the side streams before the buffers above go back to the pool.
-    const bool side = tabled && ctx->stream_aux != ctx->stream && ctx->aux_event && ctx->main_event;
-    const bool side2 = side && ctx->stream_k1 != ctx->stream && ctx->stream_k1 != ctx->stream_aux;
-    StreamDrainGuard aux_guard(ctx->stream_aux), k1_guard(ctx->stream_k1);
-    int rc = IPCFP_OK;
-    if (tabled) {
-        IPCFP_HIP(ctx, table.alloc(wit->n));
-        IPCFP_HIP(ctx, long_list.alloc(wit->n));
-        IPCFP_HIP(ctx, long_count.alloc(1));
-        IPCFP_HIP(ctx, hipMemsetAsync(long_count.p, 0, 4, ctx->stream));
-        rc = launch_hamt_list_long(ctx, wit->k1_meta.p, uint32_t(wit->n), long_list.p, long_count.p);
-        if (rc) return rc;
-        if (side) {
-            IPCFP_HIP(ctx, hipEventRecord(ctx->main_event, ctx->stream));
-            IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream_aux, ctx->main_event, 0));
-            aux_guard.armed = true;
-            hipStream_t saved = ctx->stream;
-            ctx->stream = ctx->stream_aux;  // (the launcher queues on the context's stream)
-            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
-            ctx->stream = saved;
-        } else {
-            rc = launch_hamt_node_table_lane(ctx, wit->arena.p, wit->k1_meta.p, uint32_t(wit->n), kHamtOutlineMinLen, kTableKinds, table.p);
-        }
-        if (rc) return rc;
-    }
-    // run discovery: one lane per spec, the prefix sum, and the number of runs with the call's one synchronisation
-    IPCFP_HIP(ctx, flag.alloc(n));
-    IPCFP_HIP(ctx, pos.alloc(n));
-    IPCFP_HIP(ctx, run_of.alloc(n));
-    IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
-    IPCFP_HIP(ctx, total_d.alloc(1));
-    rc = launch_sgen_run_flags(ctx, actor_d, n, flag.p);
+    SgenPrologue pro(ctx, tabled);
+    int rc = pro.discover(ctx, wit, actor_d, n);
     if (rc) return rc;
-    {
-        ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
-        rc = launch_scan_u32(ctx, flag.p, n, pos.p, total_d.p, scratch.p);
-    }
-    if (rc) return rc;
-    uint64_t n_runs = 0;
-    uint32_t n_long = 0;
-    IPCFP_HIP(ctx, d2h_small(ctx, &n_runs, total_d.p, 8, ctx->stream));
-    if (tabled) IPCFP_HIP(ctx, d2h_small(ctx, &n_long, long_count.p, 4, ctx->stream));
-    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    const uint64_t n_runs = pro.n_runs;
     if (n_runs == 0 || n_runs > n) return set_error(ctx, IPCFP_E_INVALID, "generate_storage_claims: %llu runs of %u specs", (unsigned long long)n_runs, n);
-    hipEvent_t outline_done = nullptr;
-    if (n_long) {
-        hipStream_t s = ctx->stream;
-        if (side2) {
-            s = ctx->stream_k1;
-            k1_guard.armed = true;
-            IPCFP_HIP(ctx, hipStreamWaitEvent(s, ctx->main_event, 0));
-        } else if (ctx->stream_aux != ctx->stream && ctx->aux_event) {
-            s = ctx->stream_aux;
-            aux_guard.armed = true;
-        }
-        rc = launch_hamt_outline_list(ctx, s, plain, table.p, long_list.p, long_count.p, n_long);
-        if (!rc) rc = launch_hamt_node_table_rest(ctx, s, plain, long_list.p, long_count.p, n_long, kTableKinds, table.p);
-        if (rc) return rc;
-        if (s == ctx->stream_k1) {
-            if (!ctx->outline_event) IPCFP_HIP(ctx, hipEventCreateWithFlags(&ctx->outline_event, hipEventDisableTiming));
-            outline_done = ctx->outline_event;
-            IPCFP_HIP(ctx, hipEventRecord(outline_done, s));
-        }
-    }
-    if (aux_guard.armed) IPCFP_HIP(ctx, hipEventRecord(ctx->aux_event, ctx->stream_aux));
+    rc = pro.outline(ctx, plain);
+    if (rc) return rc;
     g->n_runs = uint32_t(n_runs);
     IPCFP_HIP(ctx, runs.alloc(n_runs));
     IPCFP_HIP(ctx, g->runs_d.alloc(n_runs * IPCFP_SRUN_BYTES));
-    {
-        ProfileScope prof(ctx, IPCFP_K_SGEN_RUNS);
-        rc = launch_storage_run_heads(ctx, flag.p, pos.p, n, run_of.p, runs.p);
-    }
+    rc = pro.heads(ctx, n, runs.p);
     if (rc) return rc;
     rc = launch_sgen_run_chain(ctx, rec, child, runs.p, uint32_t(n_runs), kUndecided);
     if (rc) return rc;
-    // the table is whole from here on
-    if (aux_guard.armed) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->aux_event, 0));
-    if (outline_done) IPCFP_HIP(ctx, hipStreamWaitEvent(ctx->stream, outline_done, 0));
-    aux_guard.armed = k1_guard.armed = false;  // the main stream is ordered behind the side kernels now
-    rc = launch_sgen_run_actors(ctx, rec, tabled ? table.p : nullptr, actor_d, runs.p, uint32_t(n_runs), kUndecided);
+    rc = pro.join(ctx);
+    if (rc) return rc;
+    rc = launch_sgen_run_actors(ctx, rec, tabled ? pro.table.p : nullptr, actor_d, runs.p, uint32_t(n_runs), kUndecided);
     if (!rc) rc = launch_sgen_run_state(ctx, rec, runs.p, uint32_t(n_runs));
     DevBuf<uint32_t> root_children;  // block of every run's storage root, then the blocks behind its 32 links
     if (tabled) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 33u));
     if (!rc)
-        rc = launch_sgen_specs(ctx, rec, tabled ? table.p : nullptr, g->slot_d.p, n, run_of.p, runs.p, uint32_t(n_runs), root_children.p,
+        rc = launch_sgen_specs(ctx, rec, tabled ? pro.table.p : nullptr, g->slot_d.p, n, pro.run_of.p, runs.p, uint32_t(n_runs), root_children.p,
                                g->value_d.p, g->cflags_d.p, g->status_d.p);
     if (!rc) rc = launch_sgen_run_records(ctx, runs.p, uint32_t(n_runs), n, child, child_epoch, actor_d, g->runs_d.p);
     // the recorded blocks in BTreeSet order (synchronises: the columns are whole when it returns)
@@ -940,9 +991,208 @@ int generate_storage_claims_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint8
     return IPCFP_OK;
 }
 
+// ---- the same list of specs at every child of a chain (kernels/storage_claims_gen_tipsets.inc) --------------------------
+constexpr uint64_t kMaxRecorderWords = 1ull << 28;  // n_tipsets rows of ceil(blocks / 32) words: 1 GiB
+
+// The refusals both forms share, behind the null checks
+int sgen_tipsets_refuse(ipcfp_ctx* ctx, const ipcfp_witness* wit, uint32_t n_tipsets, uint64_t n_specs) {
+    if (n_tipsets > IPCFP_MAX_GEN_TIPSETS)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_storage_claims_tipsets: %u tipsets (at most %d)", n_tipsets, IPCFP_MAX_GEN_TIPSETS);
+    if (n_specs >= 0xffffffffULL || uint64_t(n_tipsets) * n_specs >= 0xffffffffULL)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_storage_claims_tipsets: %u tipsets of %llu specs are too many claims", n_tipsets,
+                         (unsigned long long)n_specs);
+    if (n_specs && uint64_t(n_tipsets) * div_up(wit->n, 32) > kMaxRecorderWords)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED,
+                         "generate_storage_claims_tipsets: %u recorder rows over %llu blocks exceed 2^28 words; cut the chain", n_tipsets,
+                         (unsigned long long)wit->n);
+    return IPCFP_OK;
+}
+
+// The specs are in HBM (actor_d, slot_d: the n_specs-entry list); children and epochs are the caller's host arrays.
+int generate_storage_claims_tipsets_impl(ipcfp_ctx* ctx, ipcfp_witness* wit, const uint8_t* child_cids40, const int64_t* child_epochs,
+                                         uint32_t n_tipsets, const uint64_t* actor_d, const uint8_t* slot_d, uint64_t n_specs64,
+                                         ipcfp_generated_storage_claims_t** out) {
+    std::unique_ptr<ipcfp_generated_storage_claims, void (*)(ipcfp_generated_storage_claims*)> g(
+        new (std::nothrow) ipcfp_generated_storage_claims(), ipcfp_generated_storage_claims_destroy);
+    if (!g) return set_error(ctx, IPCFP_E_NOMEM, "generate_storage_claims_tipsets: out of memory");
+    const uint64_t n64 = uint64_t(n_tipsets) * n_specs64;
+    g->ctx = ctx;
+    g->n = n64;
+    g->n_specs = n_specs64;
+    g->n_tipsets = n_tipsets;
+    g->tipset_off.assign(size_t(n_tipsets) + 1, 0);
+    if (n64 == 0) {
+        g->tipset_first_error.assign(n_tipsets, ~0ull);
+        g->have_host = true;
+        *out = g.release();
+        return IPCFP_OK;
+    }
+    const uint32_t n_specs = uint32_t(n_specs64);
+    const uint32_t words = div_up(wit->n, 32);
+    std::vector<CidKey> children(n_tipsets);
+    for (uint32_t t = 0; t < n_tipsets; ++t) children[t] = key_from_slot(child_cids40 + size_t(t) * IPCFP_CID_SLOT);
+    DevBuf<CidKey> children_d;
+    DevBuf<long long> epochs_d;
+    DevBuf<uint32_t> rows;  // the recorder: row t is tipset t's
+    IPCFP_HIP(ctx, children_d.alloc(n_tipsets));
+    IPCFP_HIP(ctx, epochs_d.alloc(n_tipsets));
+    IPCFP_HIP(ctx, rows.alloc(size_t(n_tipsets) * words));
+    IPCFP_HIP(ctx, hipMemcpyAsync(children_d.p, children.data(), size_t(n_tipsets) * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
+    static_assert(sizeof(long long) == sizeof(int64_t), "epochs are copied as they are");
+    IPCFP_HIP(ctx, hipMemcpyAsync(epochs_d.p, child_epochs, size_t(n_tipsets) * 8, hipMemcpyHostToDevice, ctx->stream));
+    IPCFP_HIP(ctx, hipMemsetAsync(rows.p, 0, size_t(n_tipsets) * words * 4, ctx->stream));
+    const WitnessView rec = witness_view(wit, rows.p);  // (every kernel offsets `touched` to its lane's row)
+    const WitnessView plain = witness_view(wit);
+    // the single call's rule, applied to all the claims of the chain
+    const int forced = ctx->hamt_table;
+    const bool tabled = forced == 1 || (forced != 0 && n64 * 16u >= wit->n);
+    IPCFP_HIP(ctx, g->slot_d.alloc(n64 * 32));
+    IPCFP_HIP(ctx, g->value_d.alloc(n64 * 32));
+    IPCFP_HIP(ctx, g->cflags_d.alloc(n64));
+    IPCFP_HIP(ctx, g->status_d.alloc(n64));
+    constexpr uint32_t kUndecided = 0xfdu;
+    DevBuf<StorageRun> runs0, runs;
+    DevBuf<uint8_t> heads;
+    SgenPrologue pro(ctx, tabled);
+    int rc = pro.discover(ctx, wit, actor_d, n_specs);  // the runs of the LIST: the same at every child
+    if (rc) return rc;
+    if (pro.n_runs == 0 || pro.n_runs > n_specs)
+        return set_error(ctx, IPCFP_E_INVALID, "generate_storage_claims_tipsets: %llu runs of %u specs", (unsigned long long)pro.n_runs, n_specs);
+    const uint32_t n_runs0 = uint32_t(pro.n_runs);
+    const uint64_t n_runs = uint64_t(n_tipsets) * n_runs0;
+    rc = pro.outline(ctx, plain);
+    if (rc) return rc;
+    g->n_runs = uint32_t(n_runs);
+    IPCFP_HIP(ctx, runs0.alloc(n_runs0));
+    IPCFP_HIP(ctx, runs.alloc(n_runs));
+    IPCFP_HIP(ctx, heads.alloc(size_t(n_tipsets) * 96));
+    IPCFP_HIP(ctx, g->runs_d.alloc(n_runs * IPCFP_SRUN_BYTES));
+    rc = pro.heads(ctx, n_specs, runs0.p);
+    if (!rc) rc = launch_sgent_runs(ctx, rec, words, children_d.p, n_tipsets, runs0.p, n_runs0, n_specs, heads.p, runs.p, kUndecided);
+    if (rc) return rc;
+    rc = pro.join(ctx);
+    if (rc) return rc;
+    const void* table = tabled ? pro.table.p : nullptr;
+    rc = launch_sgent_run_actors(ctx, rec, words, table, actor_d, runs0.p, n_runs0, n_specs, n_tipsets, runs.p, kUndecided);
+    DevBuf<uint32_t> root_children, uni, union_ids, mask, count, offset, ids_out;
+    DevBuf<uint64_t> cut_total, cut_scratch, tipset_off_d;
+    if (tabled) IPCFP_HIP(ctx, root_children.alloc(size_t(n_runs) * 33u));
+    if (!rc)
+        rc = launch_sgent_specs(ctx, rec, words, table, slot_d, pro.run_of.p, n_specs, n_runs0, n_tipsets, runs.p, root_children.p, g->slot_d.p,
+                                g->value_d.p, g->cflags_d.p, g->status_d.p);
+    if (!rc) rc = launch_sgent_run_records(ctx, runs.p, runs0.p, n_runs0, n_specs, n_tipsets, children_d.p, epochs_d.p, actor_d, g->runs_d.p);
+    // the cut: the union row through materialize (its two synchronisations, its host sort), then every tipset's own list in
+    // the union's order from the device
+    uint64_t nb = 0;
+    if (!rc) {
+        IPCFP_HIP(ctx, uni.alloc(words));
+        rc = launch_sgent_union(ctx, rows.p, n_tipsets, words, uni.p);
+    }
+    if (!rc) {
+        g->block_ids.resize(wit->n ? wit->n : 1);
+        rc = materialize(ctx, wit, uni.p, g->block_ids.data(), nullptr, g->block_ids.size(), &nb);
+    }
+    uint64_t total = 0;
+    if (!rc && nb) {
+        const uint32_t n_union = uint32_t(nb), chunks = n_tipsets * div_up(n_union, 32);
+        IPCFP_HIP(ctx, union_ids.alloc(n_union));
+        IPCFP_HIP(ctx, mask.alloc(chunks));
+        IPCFP_HIP(ctx, count.alloc(chunks));
+        IPCFP_HIP(ctx, offset.alloc(chunks));
+        IPCFP_HIP(ctx, cut_total.alloc(1));
+        IPCFP_HIP(ctx, cut_scratch.alloc(size_t(div_up(chunks, 1024)) + 2));
+        IPCFP_HIP(ctx, tipset_off_d.alloc(size_t(n_tipsets) + 1));
+        IPCFP_HIP(ctx, hipMemcpyAsync(union_ids.p, g->block_ids.data(), size_t(n_union) * 4, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_sgent_cut_count(ctx, rows.p, n_tipsets, words, uint32_t(wit->n), union_ids.p, n_union, mask.p, count.p, offset.p, cut_total.p,
+                                    cut_scratch.p);
+        if (!rc) {
+            IPCFP_HIP(ctx, d2h_small(ctx, &total, cut_total.p, 8, ctx->stream));
+            IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+            if (total > uint64_t(n_tipsets) * n_union || total >= 0xffffffffULL)
+                rc = set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_storage_claims_tipsets: %llu recorded blocks over the chain",
+                               (unsigned long long)total);
+        }
+        if (!rc) {
+            IPCFP_HIP(ctx, ids_out.alloc(total ? total : 1));
+            rc = launch_sgent_cut_fill(ctx, mask.p, offset.p, cut_total.p, n_tipsets, union_ids.p, n_union, total, ids_out.p, tipset_off_d.p);
+        }
+        if (!rc) {
+            g->tipset_ids.resize(total);
+            if (total) IPCFP_HIP(ctx, hipMemcpyAsync(g->tipset_ids.data(), ids_out.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+            IPCFP_HIP(ctx, hipMemcpyAsync(g->tipset_off.data(), tipset_off_d.p, (size_t(n_tipsets) + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    if (rc) {
+        (void)sync_stream(ctx, ctx->stream);
+        return rc;
+    }
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream, true));  // the CSR's read-back is the call's drain
+    g->block_ids.resize(nb);
+    // the offsets came from the device: they must tile the list they index
+    for (uint32_t t = 0; t < n_tipsets; ++t)
+        if (g->tipset_off[t] > g->tipset_off[t + 1] || g->tipset_off[t + 1] > total)
+            return set_error(ctx, IPCFP_E_INVALID, "generate_storage_claims_tipsets: the block list of tipset %u does not lie in the chain's", t);
+    *out = g.release();
+    return IPCFP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ipcfp_generate_storage_claims_tipsets_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cids40, const int64_t* child_epochs,
+                                                 uint32_t n_tipsets, const void* actor_ids_d, const void* slots32_d, uint64_t n_specs,
+                                                 ipcfp_generated_storage_claims_t** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !w || w->ctx != ctx || !child_cids40 || !child_epochs || !out || n_tipsets == 0 || (n_specs && (!actor_ids_d || !slots32_d)))
+        return IPCFP_E_INVALID;
+    if (const int rc = sgen_tipsets_refuse(ctx, w, n_tipsets, n_specs)) return rc;
+    if ((reinterpret_cast<uintptr_t>(slots32_d) & 15u) || (reinterpret_cast<uintptr_t>(actor_ids_d) & 7u))
+        return set_error(ctx, IPCFP_E_INVALID,
+                         "generate_storage_claims_tipsets_device: the slot column must lie on a 16-byte boundary, the actor ids on an 8-byte one");
+    IPCFP_ENTER(ctx);
+    const int rc = generate_storage_claims_tipsets_impl(ctx, w, child_cids40, child_epochs, n_tipsets, static_cast<const uint64_t*>(actor_ids_d),
+                                                        static_cast<const uint8_t*>(slots32_d), n_specs, out);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's memory)
+    return rc;
+}
+
+int ipcfp_generate_storage_claims_tipsets(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cids40, const int64_t* child_epochs,
+                                          uint32_t n_tipsets, const uint64_t* actor_ids, const uint8_t* slots32, uint64_t n_specs,
+                                          ipcfp_generated_storage_claims_t** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !w || w->ctx != ctx || !child_cids40 || !child_epochs || !out || n_tipsets == 0 || (n_specs && (!actor_ids || !slots32)))
+        return IPCFP_E_INVALID;
+    if (const int rc = sgen_tipsets_refuse(ctx, w, n_tipsets, n_specs)) return rc;
+    IPCFP_ENTER(ctx);
+    DevBuf<uint64_t> actor_d;
+    DevBuf<uint8_t> slot_d;
+    if (n_specs) {
+        IPCFP_HIP(ctx, actor_d.alloc(n_specs));
+        IPCFP_HIP(ctx, slot_d.alloc(n_specs * 32));
+        IPCFP_HIP(ctx, hipMemcpyAsync(actor_d.p, actor_ids, n_specs * 8, hipMemcpyHostToDevice, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(slot_d.p, slots32, n_specs * 32, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const int rc = generate_storage_claims_tipsets_impl(ctx, w, child_cids40, child_epochs, n_tipsets, actor_d.p, slot_d.p, n_specs, out);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's memory)
+    return rc;
+}
+
+uint32_t ipcfp_generated_storage_claims_tipset_count(const ipcfp_generated_storage_claims_t* g) { return g ? g->n_tipsets : 0; }
+uint64_t ipcfp_generated_storage_claims_tipset_first_error(ipcfp_generated_storage_claims_t* g, uint32_t t) {
+    if (!g || t >= g->n_tipsets || sgen_host_copy(g)) return ~0ull;
+    return g->tipset_first_error[t];
+}
+const uint32_t* ipcfp_generated_storage_claims_tipset_block_ids(const ipcfp_generated_storage_claims_t* g, uint32_t t, uint64_t* n) {
+    if (n) *n = 0;
+    if (!g || t >= g->n_tipsets) return nullptr;
+    if (g->tipset_off.empty()) {  // a single-child handle: its one list
+        if (n) *n = g->block_ids.size();
+        return g->block_ids.data();
+    }
+    if (n) *n = g->tipset_off[t + 1] - g->tipset_off[t];
+    return g->tipset_ids.data() + g->tipset_off[t];
+}
 
 int ipcfp_generate_storage_claims_device(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* child_cid40, int64_t child_epoch,
                                          const void* actor_ids_d, const void* slots32_d, uint64_t n, ipcfp_generated_storage_claims_t** out) {

@@ -293,6 +293,32 @@ int launch_sgen_specs(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d,
 // out_d: n_runs records of IPCFP_SRUN_BYTES
 int launch_sgen_run_records(ipcfp_ctx* ctx, const void* runs_d, uint32_t n_runs, uint32_t n, const CidKey& child, long long child_epoch,
                             const uint64_t* actor_id_d, void* out_d);
+// --- storage_claims_gen_tipsets.inc (part of storage_claims_gen.hip) --- the same for ONE spec list at each of n_tipsets
+// children.  `w`: the view whose `touched` is row 0 of the recorder, n_tipsets rows of `words` words; runs0_d / run_of0_d:
+// launch_storage_run_heads over the n_specs-entry list (n_runs0 runs); runs_d: StorageRun[n_tipsets * n_runs0], run (t, r) at
+// t * n_runs0 + r; claim (t, s) at t * n_specs + s
+// heads_d (96 bytes per tipset): child header → parent_state_root → StateRoot.actors once per tipset, then every run from it
+int launch_sgent_runs(ipcfp_ctx* ctx, const WitnessView& w, uint32_t words, const CidKey* children_d, uint32_t n_tipsets,
+                      const void* runs0_d, uint32_t n_runs0, uint32_t n_specs, void* heads_d, void* runs_d, uint32_t undecided);
+// the actor get (table_d nullable, then the walker), the EVM state and the layout sniff
+int launch_sgent_run_actors(ipcfp_ctx* ctx, const WitnessView& w, uint32_t words, const void* table_d, const uint64_t* actor_id_d,
+                            const void* runs0_d, uint32_t n_runs0, uint32_t n_specs, uint32_t n_tipsets, void* runs_d, uint32_t undecided);
+// as launch_sgen_specs; slot_d: the n_specs-entry column, slot_out_d: the handle's, written replicated
+int launch_sgent_specs(ipcfp_ctx* ctx, const WitnessView& w, uint32_t words, const void* table_d, const uint8_t* slot_d,
+                       const uint32_t* run_of0_d, uint32_t n_specs, uint32_t n_runs0, uint32_t n_tipsets, const void* runs_d,
+                       uint32_t* root_children_d, uint8_t* slot_out_d, uint8_t* value_d, uint8_t* cflags_d, uint8_t* status_d);
+int launch_sgent_run_records(ipcfp_ctx* ctx, const void* runs_d, const void* runs0_d, uint32_t n_runs0, uint32_t n_specs, uint32_t n_tipsets,
+                             const CidKey* children_d, const long long* epochs_d, const uint64_t* actor_id_d, void* out_d);
+// out_d[words] = the OR of the rows
+int launch_sgent_union(ipcfp_ctx* ctx, const uint32_t* rows_d, uint32_t n_tipsets, uint32_t words, uint32_t* out_d);
+// the per-tipset lists in the order of union_ids_d (n_union > 0 ids): per (tipset, 32 positions) a mask and its popcount,
+// their prefix sum (mask_d, count_d, offset_d: n_tipsets * div_up(n_union, 32) words; scratch_d as launch_scan_u32) …
+int launch_sgent_cut_count(ipcfp_ctx* ctx, const uint32_t* rows_d, uint32_t n_tipsets, uint32_t words, uint32_t n_blocks,
+                           const uint32_t* union_ids_d, uint32_t n_union, uint32_t* mask_d, uint32_t* count_d, uint32_t* offset_d,
+                           uint64_t* total_d, uint64_t* scratch_d);
+// … and the lists themselves: ids_out_d[cap], tipset_off_d[n_tipsets + 1]
+int launch_sgent_cut_fill(ipcfp_ctx* ctx, const uint32_t* mask_d, const uint32_t* offset_d, const uint64_t* total_d, uint32_t n_tipsets,
+                          const uint32_t* union_ids_d, uint32_t n_union, uint64_t cap, uint32_t* ids_out_d, uint64_t* tipset_off_d);
 
 // --- shard.hip ---
 int launch_plan_receipts(ipcfp_ctx* ctx, const WitnessView& rec, const CidKey& receipts_root, uint64_t lo, uint32_t n);

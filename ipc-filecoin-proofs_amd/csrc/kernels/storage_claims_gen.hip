@@ -429,3 +429,5 @@ int launch_sgen_run_records(ipcfp_ctx* ctx, const void* runs_d, uint32_t n_runs,
 }
 
 }  // namespace ipcfp
+
+#include "storage_claims_gen_tipsets.inc"  // the same for a chain of child headers, on the helpers above
