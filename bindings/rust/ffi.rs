@@ -685,6 +685,56 @@ impl Witness<'_> {
         Ok((out, block_ids))
     }
 
+    /// `generate_event_proof` for a CHAIN of tipset pairs in one pass (`ipcfp_generate_event_claims_tipsets`, at most
+    /// `IPCFP_MAX_GEN_TIPSETS` pairs in chain order).  Per tipset `Ok(its EventProofs)` or `Err(status)` — exactly what the
+    /// single call answers for that pair; a failing tipset contributes nothing and changes nothing about the others.  The
+    /// block ids are the union of what the SOUND tipsets recorded, in `Cid: Ord` order.  (The handle also keeps the keys as
+    /// they were given, `ipcfp_generated_events_tipsets`: what `claim.tipset` indexes when the packed claims are verified.)
+    pub fn generate_event_proofs_tipsets(&self, pairs: &[(Vec<Cid>, Cid)], filter: &ipcfp_event_filter_t,
+                                         actor_id_filter: Option<u64>) -> Result<(Vec<std::result::Result<Vec<EventProof>, u8>>, Vec<u32>)> {
+        if pairs.is_empty() || pairs.len() > IPCFP_MAX_GEN_TIPSETS { return Err(anyhow!("generate_event_proofs_tipsets takes 1 to {IPCFP_MAX_GEN_TIPSETS} tipsets")); }
+        let (mut pc, mut children, mut off) = (Vec::new(), Vec::new(), vec![0u32]);
+        for (parents, child) in pairs {
+            for c in parents { pc.extend_from_slice(&cid_slot(c)?); }
+            children.extend_from_slice(&cid_slot(child)?);
+            off.push((pc.len() / IPCFP_CID_SLOT) as u32);
+        }
+        if pc.is_empty() { pc.resize(IPCFP_CID_SLOT, 0); }
+        let mut g = std::ptr::null_mut::<ipcfp_generated_events_t>();
+        let rc = unsafe { ipcfp_generate_event_claims_tipsets(self.eng.ctx, self.raw(), pc.as_ptr(), off.as_ptr(), children.as_ptr(), pairs.len() as u32,
+                                                              filter, actor_id_filter.is_some() as c_int, actor_id_filter.unwrap_or(0), &mut g) };
+        if rc != 0 || g.is_null() { return Err(self.eng.err("ipcfp_generate_event_claims_tipsets", rc)); }
+        struct Guard(*mut ipcfp_generated_events_t);
+        impl Drop for Guard { fn drop(&mut self) { unsafe { ipcfp_generated_events_destroy(self.0) } } }
+        let _guard = Guard(g);
+        let t = unsafe { ipcfp_generated_events_tipset_count(g) } as usize;
+        let mut nt = 0u32;
+        let st = unsafe { std::slice::from_raw_parts(ipcfp_generated_events_tipset_status(g, &mut nt), t) };
+        let coff = unsafe { std::slice::from_raw_parts(ipcfp_generated_events_tipset_claim_off(g, &mut nt), t + 1) };
+        let (mut proofs, mut n, mut bad) = (std::ptr::null::<ipcfp_event_proof_t>(), 0u64, u64::MAX);
+        let rc = unsafe { ipcfp_generated_events_proofs(g, &mut proofs, &mut n, &mut bad) };
+        if rc != 0 { return Err(anyhow!("{} (proof {bad})", self.eng.err("ipcfp_generated_events_proofs", rc))); }
+        let s = |p: *const c_char| unsafe { CStr::from_ptr(p) }.to_string_lossy().into_owned();
+        let list = |p: *const *const c_char, n: u32| (0..n as usize).map(|k| s(unsafe { *p.add(k) })).collect::<Vec<String>>();
+        let mut out = Vec::with_capacity(t);
+        for k in 0..t {
+            if st[k] != IPCFP_ST_TRUE { out.push(Err(st[k])); continue; }
+            let mut mine = Vec::new();
+            for i in coff[k] as usize..coff[k + 1] as usize {
+                let p = unsafe { &*proofs.add(i) };
+                mine.push(EventProof {
+                    parent_epoch: p.parent_epoch, child_epoch: p.child_epoch, parent_tipset_cids: list(p.parent_tipset_cids, p.n_parent_tipset_cids),
+                    child_block_cid: s(p.child_block_cid), message_cid: s(p.message_cid), exec_index: p.exec_index, event_index: p.event_index,
+                    event_data: EventData { emitter: p.emitter, topics: list(p.topics, p.n_topics), data: s(p.data) } });
+            }
+            out.push(Ok(mine));
+        }
+        let mut nb = 0u64;
+        let ids = unsafe { ipcfp_generated_events_block_ids(g, &mut nb) };
+        let block_ids = if nb == 0 { Vec::new() } else { unsafe { std::slice::from_raw_parts(ids, nb as usize) }.to_vec() };
+        Ok((out, block_ids))
+    }
+
     /// `generate_storage_proof` for a batch of specs of one child block (src/proofs/storage/generator.rs:29-178), in the
     /// order `generate_proof_bundle` walks them: the device leaves the proofs as column claims in HBM
     /// (`ipcfp_generate_storage_claims`) and the library spells them (`ipcfp_generated_storage_claims_proofs`).  Returns the

@@ -192,7 +192,8 @@ enum {
     IPCFP_K_SCAN_MULTI_FILL = 23,  /* … PASS 2: the has-map, matches + match_spec, per-spec counts */
     IPCFP_K_SCAN_MULTI_TAIL = 24,  /* … the table route's tail in one launch: look-back prefix sum, map, fill, counts, mailbox */
     IPCFP_K_SCAN_TIPSETS = 25,     /* ipcfp_scan_events_tipsets*: tipset boundaries, PASS 1 / PASS 2 over the leaves of a chain */
-    IPCFP_K_COUNT = 26
+    IPCFP_K_GEN_TIPSETS = 26,      /* ipcfp_generate_event_claims_tipsets: chain prologue, segmented execution order, gather, marks, patch */
+    IPCFP_K_COUNT = 27
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -1023,6 +1024,35 @@ uint32_t ipcfp_generated_storage_claims_tipset_count(const ipcfp_generated_stora
 uint64_t ipcfp_generated_storage_claims_tipset_first_error(ipcfp_generated_storage_claims_t* g, uint32_t t);
 const uint32_t* ipcfp_generated_storage_claims_tipset_block_ids(const ipcfp_generated_storage_claims_t* g, uint32_t t,
                                                                 uint64_t* n);
+
+/* ipcfp_generate_event_claims for a CHAIN of tipset pairs in one pass.  Tipset t is the pair (parent_cids40[parent_off[t] ..
+ * parent_off[t + 1]), child_cids40[t]) in chain order (parent_off: n_tipsets + 1 slot counts ascending from 0; all arrays in
+ * host memory).  Returns IPCFP_OK and a handle whatever the tipsets' statuses are.  The handle holds what n_tipsets single
+ * calls with the same filter on the same witness give, laid end to end in tipset order: claims, match records and message
+ * CIDs of tipset t are byte for byte the single call's except that claim.tipset = t, topics_off / data_off are shifted by
+ * the start of tipset t's segment in the one tight blob, and parent_epoch / child_epoch are that tipset's own.
+ *   a failing tipset   (its single call's *status_out is not IPCFP_ST_TRUE) contributes no claim, no blob byte and no recorded
+ *                      block and changes nothing about any other tipset; the same pair given twice is two tipsets
+ *   _tipset_count      n_tipsets (1 for a handle of the single call)
+ *   _tipsets           n_tipsets ipcfp_tipset_ref_t, one per INPUT tipset (claim.tipset indexes it), both parsed flags set,
+ *                      wide keys behind more_parents (owned by the handle); _tipset keeps returning entry 0
+ *   _tipset_status     per tipset exactly the single call's *status_out
+ *   _tipset_claim_off  n_tipsets + 1 offsets into the claim list (*n = n_tipsets; an empty range: a failing tipset, or no match)
+ *   _block_ids         the union of the blocks the SOUND tipsets recorded, each once, in `Cid: Ord` order
+ * IPCFP_E_INVALID: a null mandatory pointer, n_tipsets == 0, parent_off not ascending from 0, a witness with a receipt range
+ * set.  IPCFP_E_UNSUPPORTED: n_tipsets > IPCFP_MAX_GEN_TIPSETS; more than 65 535 message-tree roots over the chain (2 per
+ * parent block: the enumerator's error word orders 2^16 roots); a tipset key of more than IPCFP_MAX_PARENTS_WIDE blocks;
+ * 2^31 - 1 or more receipts, 2^32 - 1 or more matches or raw message positions over the chain; a blob of 3.75 GB or more.
+ * After any refusal *out is NULL.  The call neither reads nor fills the witness's per-root caches, the scan hint or the
+ * block table's filter.                                                                                               */
+int ipcfp_generate_event_claims_tipsets(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* parent_cids40,
+                                        const uint32_t* parent_off, const uint8_t* child_cids40, uint32_t n_tipsets,
+                                        const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor,
+                                        ipcfp_generated_events_t** out);
+uint32_t ipcfp_generated_events_tipset_count(const ipcfp_generated_events_t* g);
+const ipcfp_tipset_ref_t* ipcfp_generated_events_tipsets(const ipcfp_generated_events_t* g, uint32_t* n);
+const ipcfp_status_t* ipcfp_generated_events_tipset_status(const ipcfp_generated_events_t* g, uint32_t* n);
+const uint64_t* ipcfp_generated_events_tipset_claim_off(const ipcfp_generated_events_t* g, uint32_t* n);
 
 /* The host inverse of ipcfp_pack_storage_proofs (no device, no context): packed claims → StorageProof structs with the
  * strings the reference writes — every CID `Cid::to_string()`, slot and value `format!("0x{}", hex::encode(..))`

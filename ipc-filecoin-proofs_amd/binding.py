@@ -108,6 +108,7 @@ KERNEL_IDS = {
     "scan_multi_fill": 23,
     "scan_multi_tail": 24,
     "scan_tipsets": 25,
+    "gen_tipsets": 26,
 }
 
 MAX_SCAN_SPECS = 1024
@@ -391,6 +392,11 @@ def load_library() -> C.CDLL:
         "ipcfp_verify_proof_bundle": (i32, [vp, vp, vp, vp, vp, vp]),
         "ipcfp_event_claims_from_matches_device": (i32, [vp, vp, vp, u64, vp, C.c_int64, C.c_int64, C.c_uint32, vp, vp, u64, C.POINTER(u64)]),
         "ipcfp_generate_event_claims": (i32, [vp, vp, vp, C.c_uint32, vp, vp, i32, u64, vp, C.POINTER(vp)]),
+        "ipcfp_generate_event_claims_tipsets": (i32, [vp, vp, vp, vp, vp, C.c_uint32, vp, i32, u64, C.POINTER(vp)]),
+        "ipcfp_generated_events_tipset_count": (C.c_uint32, [vp]),
+        "ipcfp_generated_events_tipsets": (vp, [vp, C.POINTER(C.c_uint32)]),
+        "ipcfp_generated_events_tipset_status": (vp, [vp, C.POINTER(C.c_uint32)]),
+        "ipcfp_generated_events_tipset_claim_off": (vp, [vp, C.POINTER(C.c_uint32)]),
         "ipcfp_generated_events_destroy": (None, [vp]),
         "ipcfp_generated_events_count": (u64, [vp]),
         "ipcfp_generated_events_tipset": (vp, [vp]),
@@ -1100,8 +1106,16 @@ class GeneratedEvents:
         self.claims_ptr = lib.ipcfp_generated_events_claims_device(handle) or 0
         self.blob_ptr = lib.ipcfp_generated_events_blob_device(handle, C.byref(bl)) or 0
         self.blob_len = int(bl.value)
-        buf = (C.c_uint8 * TIPSET_DTYPE.itemsize).from_address(lib.ipcfp_generated_events_tipset(handle))
-        self.tipsets = np.frombuffer(buf, dtype=TIPSET_DTYPE)  # one record; more_parents points into the handle
+        # one record per INPUT tipset (the single call: one); more_parents points into the handle
+        nt = C.c_uint32()
+        pt = lib.ipcfp_generated_events_tipsets(handle, C.byref(nt))
+        self.tipset_count = int(lib.ipcfp_generated_events_tipset_count(handle))
+        buf = (C.c_uint8 * (TIPSET_DTYPE.itemsize * nt.value)).from_address(pt)
+        self.tipsets = np.frombuffer(buf, dtype=TIPSET_DTYPE)
+        ps = lib.ipcfp_generated_events_tipset_status(handle, C.byref(nt))
+        self.tipset_status = np.frombuffer((C.c_uint8 * nt.value).from_address(ps), dtype=np.uint8).copy()
+        po = lib.ipcfp_generated_events_tipset_claim_off(handle, C.byref(nt))
+        self.tipset_claim_off = np.frombuffer((C.c_uint8 * (8 * (nt.value + 1))).from_address(po), dtype=np.uint64).copy()
         nb = C.c_uint64()
         pb = lib.ipcfp_generated_events_block_ids(handle, C.byref(nb))
         self.block_ids = (np.frombuffer((C.c_uint8 * (4 * nb.value)).from_address(pb), dtype=np.uint32).copy() if nb.value
@@ -1788,6 +1802,24 @@ class Witness:
         self.eng._check(self.lib.ipcfp_generate_event_claims(self.eng.h, self.h, _p(pc), len(parent_cids), _p(child), _p(filt),
                                                              a[0], a[1], _p(st), C.byref(h)), "generate_event_claims")
         return int(st[0]), (GeneratedEvents(self.eng, h) if h.value else None)
+
+    def generate_event_claims_tipsets(self, pairs, topic0: bytes, topic1: bytes, actor=None) -> "GeneratedEvents":
+        """generate_event_claims for a CHAIN of tipset pairs in one pass (ipcfp_generate_event_claims_tipsets).
+        pairs: [(parent CIDs, child CID), …] in chain order.  → GeneratedEvents over the whole chain: what the single
+        calls give laid end to end, with `tipset_count`, `tipsets`, `tipset_status` and `tipset_claim_off`; a failing
+        tipset contributes nothing."""
+        off = np.zeros(len(pairs) + 1, dtype=np.uint32)
+        for t, (parents, _) in enumerate(pairs):
+            off[t + 1] = off[t] + len(parents)
+        flat = [c for parents, _ in pairs for c in parents]
+        pc = cid_slots(flat) if flat else np.zeros((1, CID_SLOT), dtype=np.uint8)
+        children = cid_slots([child for _, child in pairs]) if len(pairs) else np.zeros((1, CID_SLOT), dtype=np.uint8)
+        filt = np.frombuffer(bytes(topic0) + bytes(topic1), dtype=np.uint8).copy()
+        h = C.c_void_p()
+        a = (0, 0) if actor is None else (1, int(actor))
+        self.eng._check(self.lib.ipcfp_generate_event_claims_tipsets(self.eng.h, self.h, _p(pc), _p(off), _p(children), len(pairs),
+                                                                     _p(filt), a[0], a[1], C.byref(h)), "generate_event_claims_tipsets")
+        return GeneratedEvents(self.eng, h)
 
     def event_claims_from_matches_device(self, matches_ptr: int, n: int, message_cids_ptr: int, parent_epoch: int, child_epoch: int,
                                          tipset: int, claims_out_ptr: int, blob_out_ptr: int, cap_blob: int):

@@ -24,7 +24,9 @@
 #include "../kernels/launch.h"
 #include "../kernels/storage_runs.h"
 #include "exec_state.h"
+#include "gen_tipsets_layout.h"
 #include "scan_events_multi.h"
+#include "scan_events_tipsets.h"
 #include "tipset_wide.h"
 
 using namespace ipcfp;
@@ -383,8 +385,11 @@ struct ipcfp_generated_events {
     DevBuf<uint8_t> blob_d;
     DevBuf<ipcfp_event_match_t> matches_d;
     DevBuf<CidKey> msg_d;
-    ipcfp_tipset_ref_t tipset;
-    std::vector<uint8_t> more_parents;
+    // one entry per INPUT tipset (the single call: one); claim.tipset indexes `tipsets`
+    std::vector<ipcfp_tipset_ref_t> tipsets;
+    std::vector<std::vector<uint8_t>> more_parents;  // per tipset: the slots behind the inline form
+    std::vector<ipcfp_status_t> tipset_status;
+    std::vector<uint64_t> claim_off;  // n_tipsets + 1
     std::vector<uint32_t> block_ids;
     // host copies, made on first use
     bool have_host = false;
@@ -396,6 +401,29 @@ struct ipcfp_generated_events {
 };
 
 namespace {
+
+// the tipsets the claims name: the keys as they were given (a folded slot stays folded).  parent_off: nullable for ONE tipset
+void generated_set_tipsets(ipcfp_generated_events* g, const uint8_t* parent_cids40, const uint32_t* parent_off, uint32_t n_parents_one,
+                           const uint8_t* child_cids40, uint32_t n_tipsets) {
+    g->tipsets.resize(n_tipsets);
+    g->more_parents.assign(n_tipsets, {});
+    for (uint32_t t = 0; t < n_tipsets; ++t) {
+        ipcfp_tipset_ref_t& ref = g->tipsets[t];
+        const uint32_t first = parent_off ? parent_off[t] : 0u;
+        const uint32_t n_parents = parent_off ? parent_off[t + 1] - first : n_parents_one;
+        const uint8_t* parents = n_parents ? parent_cids40 + size_t(first) * IPCFP_CID_SLOT : nullptr;
+        std::memset(&ref, 0, sizeof ref);
+        ref.flags = TC_PARENTS_PARSED | TC_CHILD_PARSED;
+        ref.n_parents = n_parents;
+        std::memcpy(ref.child, child_cids40 + size_t(t) * IPCFP_CID_SLOT, IPCFP_CID_SLOT);
+        const uint32_t n_inline = n_parents < uint32_t(IPCFP_MAX_PARENTS) ? n_parents : uint32_t(IPCFP_MAX_PARENTS);
+        if (n_inline) std::memcpy(ref.parents, parents, size_t(n_inline) * IPCFP_CID_SLOT);
+        if (n_parents > n_inline) {
+            g->more_parents[t].assign(parents + size_t(n_inline) * IPCFP_CID_SLOT, parents + size_t(n_parents) * IPCFP_CID_SLOT);
+            ref.more_parents = g->more_parents[t].data();
+        }
+    }
+}
 
 int generated_host_copy(ipcfp_generated_events* g) {
     if (g->have_host) return IPCFP_OK;
@@ -414,6 +442,302 @@ int generated_host_copy(ipcfp_generated_events* g) {
         IPCFP_HIP(ctx, hipMemcpyAsync(g->blob_h.data(), g->blob_d.p, g->blob_len, hipMemcpyDeviceToHost, ctx->stream));
     IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
     g->have_host = true;
+    return IPCFP_OK;
+}
+
+// ---- generate_event_proof for a CHAIN of tipset pairs (ipcfp_generate_event_claims_tipsets; kernels/event_gen_tipsets.inc) ----
+
+// host mirrors of the kernels' per-tipset records
+struct GentTipsetHost {
+    uint32_t slot_first, root_first, n_parents, dead;
+};
+struct GentFactsHost {
+    CidKey receipts_root;
+    long long child_height, parent0_height;
+    unsigned long long err;
+    uint32_t child_status, pad;
+};
+static_assert(sizeof(GentTipsetHost) == 16 && sizeof(GentFactsHost) == 72, "kernels/event_gen_tipsets.inc GentTipset / GentFacts");
+
+// what the chain's arguments say, built once and read by every pass
+struct GentChain {
+    uint32_t T = 0, n_roots = 0, n_slots = 0;
+    const uint32_t* parent_off = nullptr;
+    std::vector<CidKey> parents, children;
+    std::vector<uint32_t> seq_tipset;  // root number → tipset
+    DevBuf<CidKey> parents_d;
+    DevBuf<uint32_t> seq_tipset_d;
+};
+
+// what one pass over the chain leaves behind: statuses on the host, matches and their message CIDs on the device
+struct GentPass {
+    std::vector<uint32_t> status;  // per tipset: the single call's *status_out
+    std::vector<GentFactsHost> facts;
+    TipsetsScanResult scan;        // scan.matches_p, scan.match_off: the records of the sound tipsets end to end
+    DevBuf<CidKey> msg;
+    uint64_t nm = 0;
+    // host memory the pass's queued copies read or write (alive until the pass's last synchronisation)
+    std::vector<TipsetCtxDev> ctxs;
+    std::vector<GentTipsetHost> tips;
+    std::vector<uint8_t> roots40, skip;
+    std::vector<CidKey> base;
+    std::vector<uint32_t> base_tip, flags;
+};
+
+// One pass: prologue, the message trees, the segmented execution order, the scan, the gather, the base marks — recording
+// into `touched_d`.  `dead` (nullable): tipsets that are not looked at at all; their status is taken from `dead_status`.
+int gent_pass(ipcfp_ctx* ctx, ipcfp_witness* w, const GentChain& ch, const ipcfp_event_filter_t* filter, int has_actor, uint64_t actor,
+              uint32_t* touched_d, const uint8_t* dead, const uint32_t* dead_status, GentPass& ps) {
+    const uint32_t T = ch.T;
+    const WitnessView rec = witness_view(w, touched_d);
+    ps.status.assign(T, IPCFP_ST_TRUE);
+    ps.facts.assign(T, GentFactsHost{});
+    // ---- the chain prologue: every header, every TxMeta, every message-AMT root; ONE synchronisation ----
+    ps.ctxs.assign(T, TipsetCtxDev{});
+    ps.tips.resize(T);
+    for (uint32_t t = 0; t < T; ++t) {
+        const uint32_t first = ch.parent_off[t], P = ch.parent_off[t + 1] - first;
+        TipsetCtxDev& tc = ps.ctxs[t];
+        tc.flags = TC_PARENTS_PARSED | TC_CHILD_PARSED;
+        tc.n_parents = P;
+        tc.child = ch.children[t];
+        for (uint32_t j = 0; j < P && j < uint32_t(IPCFP_MAX_PARENTS); ++j) tc.parents[j] = ch.parents[first + j];
+        if (tipset_is_wide(P)) tc.parents_wide = ch.parents_d.p + first;  // (the whole key in HBM: tipset_ctx.h)
+        ps.tips[t] = GentTipsetHost{2u * t + first, 2u * first, P, dead && dead[t] ? 1u : 0u};
+    }
+    DevBuf<TipsetCtxDev> ctxs_d;
+    DevBuf<GentTipsetHost> tips_d;
+    DevBuf<GentFactsHost> facts_d;
+    DevBuf<AmtRootSpec> roots;
+    DevBuf<unsigned long long> err_d, enum_err;
+    IPCFP_HIP(ctx, ctxs_d.alloc(T));
+    IPCFP_HIP(ctx, tips_d.alloc(T));
+    IPCFP_HIP(ctx, facts_d.alloc(T));
+    IPCFP_HIP(ctx, roots.alloc(size_t(ch.n_roots) + 1));
+    IPCFP_HIP(ctx, err_d.alloc(T));
+    IPCFP_HIP(ctx, enum_err.alloc(1));
+    IPCFP_HIP(ctx, hipMemcpyAsync(ctxs_d.p, ps.ctxs.data(), size_t(T) * sizeof(TipsetCtxDev), hipMemcpyHostToDevice, ctx->stream));
+    IPCFP_HIP(ctx, hipMemcpyAsync(tips_d.p, ps.tips.data(), size_t(T) * sizeof(GentTipsetHost), hipMemcpyHostToDevice, ctx->stream));
+    IPCFP_HIP(ctx, hipMemsetAsync(err_d.p, 0xff, size_t(T) * 8, ctx->stream));
+    int rc = launch_gent_prologue(ctx, rec, ctxs_d.p, tips_d.p, T, ch.n_slots, roots.p, err_d.p, facts_d.p);
+    if (rc) return rc;
+    IPCFP_HIP(ctx, hipMemcpyAsync(ps.facts.data(), facts_d.p, size_t(T) * sizeof(GentFactsHost), hipMemcpyDeviceToHost, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    for (uint32_t t = 0; t < T; ++t) {
+        if (ps.tips[t].dead) ps.status[t] = dead_status[t];
+        else if (ps.facts[t].child_status != IPCFP_ST_TRUE) ps.status[t] = ps.facts[t].child_status;  // generator.rs:89-95
+    }
+    // ---- the message trees, all together; one more round per failing tipset (as host/scan_events_tipsets.cpp) ----
+    AmtEnumResult en;
+    if (ch.n_roots) {
+        std::vector<uint8_t> named(T, 0);
+        for (uint32_t round = 0;; ++round) {
+            IPCFP_HIP(ctx, hipMemsetAsync(enum_err.p, 0xff, 8, ctx->stream));
+            rc = amt_enumerate(ctx, rec, roots.p, ch.n_roots, VK_CID, enum_err.p, en);
+            if (rc) return rc;
+            if (en.error == kNoEnumError) break;
+            const uint32_t g = uint32_t(en.error >> 48);
+            const uint32_t t = g < ch.n_roots ? ch.seq_tipset[g] : T;
+            if (t >= T || named[t] || ps.status[t] != IPCFP_ST_TRUE || round >= T)
+                return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: the enumerator names root %u twice", g);
+            named[t] = 1;
+            // the single call's word: the same failure under the tipset's own sequence number, merged with its stage 1
+            const uint32_t local = g - ps.tips[t].root_first;
+            const uint64_t seq = uint64_t(ps.tips[t].n_parents) + 3ull * (local / 2u) + 1ull + (local & 1u);
+            const uint64_t own = (en.error & 0x0000ffffffffffffull) | ((seq & 0xffffull) << 48);
+            ps.status[t] = enum_error_code(own < ps.facts[t].err ? own : ps.facts[t].err);
+            rc = launch_gent_skip_roots(ctx, roots.p, ps.tips[t].root_first, ps.tips[t].root_first + 2u * ps.tips[t].n_parents);
+            if (rc) return rc;
+        }
+    }
+    for (uint32_t t = 0; t < T; ++t)
+        if (ps.status[t] == IPCFP_ST_TRUE && ps.facts[t].err != kNoEnumError) ps.status[t] = enum_error_code(ps.facts[t].err);
+    if (en.n_leaves >= 0xffffffffull)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: 2^32 - 1 or more raw message positions over the chain");
+    const uint32_t n = uint32_t(en.n_leaves);
+    // ---- the segmented execution order: one table, one prefix sum, the lists end to end ----
+    DevBuf<CidKey> keys, list;
+    DevBuf<uint32_t> tip, first, pos, first_by_root, exec_off;
+    DevBuf<unsigned long long> slots;
+    DevBuf<uint64_t> scratch, total;
+    IPCFP_HIP(ctx, exec_off.alloc(size_t(T) + 1));
+    IPCFP_HIP(ctx, first_by_root.alloc(size_t(ch.n_roots) + 1));
+    IPCFP_HIP(ctx, total.alloc(1));
+    IPCFP_HIP(ctx, hipMemsetAsync(total.p, 0, 8, ctx->stream));
+    IPCFP_HIP(ctx, list.alloc(n ? n : 1));
+    if (n) {
+        const uint32_t size = exec_table_size(n);
+        IPCFP_HIP(ctx, keys.alloc(n));
+        IPCFP_HIP(ctx, tip.alloc(n));
+        IPCFP_HIP(ctx, first.alloc(n));
+        IPCFP_HIP(ctx, pos.alloc(n));
+        IPCFP_HIP(ctx, slots.alloc(size));
+        IPCFP_HIP(ctx, scratch.alloc(size_t(div_up(n, 1024)) + 2));
+        IPCFP_HIP(ctx, hipMemsetAsync(slots.p, 0xff, size_t(size) * 8, ctx->stream));
+        IPCFP_HIP(ctx, hipMemsetAsync(first.p, 0, size_t(n) * 4, ctx->stream));
+        rc = launch_tipset_bounds(ctx, en.leaves.p, n, ch.n_roots, first_by_root.p);
+        if (rc) return rc;
+        rc = launch_gent_exec_order(ctx, rec, en.leaves.p, n, ch.seq_tipset_d.p, ch.n_roots, keys.p, tip.p, slots.p, size - 1, first.p);
+        if (rc) return rc;
+        rc = launch_scan_u32(ctx, first.p, n, pos.p, total.p, scratch.p);
+        if (rc) return rc;
+        rc = launch_exec_compact(ctx, keys.p, n, first.p, pos.p, list.p);
+        if (rc) return rc;
+    }
+    rc = launch_gent_exec_ranges(ctx, tips_d.p, T, first_by_root.p, pos.p, total.p, n, exec_off.p);
+    if (rc) return rc;
+    // ---- the scan of the tipsets still sound (generator.rs:137-150), recording ----
+    ps.roots40.assign(size_t(T) * IPCFP_CID_SLOT, 0);
+    ps.skip.assign(T, 0);
+    for (uint32_t t = 0; t < T; ++t) {
+        if (ps.status[t] != IPCFP_ST_TRUE) ps.skip[t] = 1;
+        else std::memcpy(ps.roots40.data() + size_t(t) * IPCFP_CID_SLOT, ps.facts[t].receipts_root.w, IPCFP_CID_SLOT);
+    }
+    const uint8_t has_actor8 = has_actor ? 1 : 0;
+    rc = scan_events_tipsets_device(ctx, w, ps.roots40.data(), T, filter, &has_actor8, &actor, 1, touched_d, ps.scan, 0, ~0ull, ps.skip.data());
+    if (rc) return rc;  // (the stream is drained)
+    for (uint32_t t = 0; t < T; ++t)
+        if (!ps.skip[t] && ps.scan.status[t] != IPCFP_ST_TRUE) ps.status[t] = ps.scan.status[t];
+    if (ps.scan.layout.n_receipts >= 0x7fffffffull)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: 2^31 - 1 or more receipts over the chain");
+    ps.nm = ps.scan.layout.n_matches;  // (< 2^32 - 1: the scan's layout refuses more)
+    // ---- message CID of each match (generator.rs:152-169) and the base witness (:97-112) of the tipsets still sound ----
+    DevBuf<uint64_t> match_off_d;
+    DevBuf<uint32_t> flags_d, base_tip_d;  // flags: [0, T) outside the execution order, [T, 2T) a base CID is absent
+    DevBuf<CidKey> base_d;
+    IPCFP_HIP(ctx, flags_d.alloc(2 * size_t(T)));
+    IPCFP_HIP(ctx, hipMemsetAsync(flags_d.p, 0, 2 * size_t(T) * 4, ctx->stream));
+    if (ps.nm) {
+        IPCFP_HIP(ctx, match_off_d.alloc(size_t(T) + 1));
+        IPCFP_HIP(ctx, hipMemcpyAsync(match_off_d.p, ps.scan.match_off.data(), (size_t(T) + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        IPCFP_HIP(ctx, ps.msg.alloc(ps.nm));
+        rc = launch_gent_gather(ctx, ps.scan.matches_p, uint32_t(ps.nm), match_off_d.p, T, exec_off.p, list.p, ps.msg.p, flags_d.p);
+        if (rc) return rc;
+    }
+    ps.base.clear();
+    ps.base_tip.clear();
+    for (uint32_t t = 0; t < T; ++t) {
+        if (ps.status[t] != IPCFP_ST_TRUE) continue;
+        for (uint32_t j = ch.parent_off[t]; j < ch.parent_off[t + 1]; ++j) ps.base.push_back(ch.parents[j]);
+        ps.base.push_back(ch.children[t]);
+        ps.base.push_back(ps.facts[t].receipts_root);
+        ps.base_tip.resize(ps.base.size(), t);
+    }
+    if (!ps.base.empty()) {
+        IPCFP_HIP(ctx, base_d.alloc(ps.base.size()));
+        IPCFP_HIP(ctx, base_tip_d.alloc(ps.base.size()));
+        IPCFP_HIP(ctx, hipMemcpyAsync(base_d.p, ps.base.data(), ps.base.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(base_tip_d.p, ps.base_tip.data(), ps.base_tip.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_gent_mark_base(ctx, rec, base_d.p, base_tip_d.p, uint32_t(ps.base.size()), flags_d.p + T);
+        if (rc) return rc;
+    }
+    ps.flags.assign(2 * size_t(T), 0);
+    IPCFP_HIP(ctx, hipMemcpyAsync(ps.flags.data(), flags_d.p, ps.flags.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+    for (uint32_t t = 0; t < T; ++t) {
+        if (ps.status[t] != IPCFP_ST_TRUE) continue;
+        if (ps.flags[t]) ps.status[t] = IPCFP_ST_ERR;  // "Missing message at index" (generator.rs:158-160) precedes materialisation
+        else if (ps.flags[size_t(T) + t]) ps.status[t] = IPCFP_ST_ERR_MISSING_BLOCK;  // must_get of a base CID (witness.rs:45-48)
+    }
+    return IPCFP_OK;
+}
+
+// The body behind the argument checks.  Pass 1 looks at every tipset and records optimistically; when a tipset failed, the
+// bitmap is cleared and pass 2 runs with every failing tipset skipped, so that the recorder — ONE bitmap — ends up holding
+// only what sound tipsets recorded.  A sound chain runs one pass.
+int generate_events_tipsets_body(ipcfp_ctx* ctx, ipcfp_witness* w, GentChain& ch, const ipcfp_event_filter_t* filter, int has_actor,
+                                 uint64_t actor, ipcfp_generated_events* g) {
+    const uint32_t T = ch.T;
+    const uint32_t words = div_up(uint32_t(w->n), 32);
+    DevBuf<uint32_t> touched;
+    IPCFP_HIP(ctx, touched.alloc(words ? words : 1));
+    IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words) * 4, ctx->stream));
+    IPCFP_HIP(ctx, ch.parents_d.alloc(ch.parents.size() ? ch.parents.size() : 1));
+    IPCFP_HIP(ctx, ch.seq_tipset_d.alloc(ch.seq_tipset.size() ? ch.seq_tipset.size() : 1));
+    if (!ch.parents.empty())
+        IPCFP_HIP(ctx, hipMemcpyAsync(ch.parents_d.p, ch.parents.data(), ch.parents.size() * sizeof(CidKey), hipMemcpyHostToDevice, ctx->stream));
+    if (!ch.seq_tipset.empty())
+        IPCFP_HIP(ctx, hipMemcpyAsync(ch.seq_tipset_d.p, ch.seq_tipset.data(), ch.seq_tipset.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    std::unique_ptr<GentPass> ps(new GentPass());
+    int rc = gent_pass(ctx, w, ch, filter, has_actor, actor, touched.p, nullptr, nullptr, *ps);
+    if (rc) return rc;
+    uint32_t failing = 0;
+    for (uint32_t t = 0; t < T; ++t) failing += ps->status[t] != IPCFP_ST_TRUE;
+    if (failing && failing < T) {
+        std::vector<uint8_t> dead(T);
+        const std::vector<uint32_t> status1 = ps->status;
+        for (uint32_t t = 0; t < T; ++t) dead[t] = status1[t] != IPCFP_ST_TRUE;
+        IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words) * 4, ctx->stream));
+        ps.reset(new GentPass());
+        rc = gent_pass(ctx, w, ch, filter, has_actor, actor, touched.p, dead.data(), status1.data(), *ps);
+        if (rc) return rc;
+        for (uint32_t t = 0; t < T; ++t)
+            if (ps->status[t] != status1[t])
+                return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: tipset %u answers %u alone and %u beside failing tipsets", t,
+                                 ps->status[t], status1[t]);
+    } else if (failing) {  // every tipset fails: nothing is claimed, nothing recorded
+        IPCFP_HIP(ctx, hipMemsetAsync(touched.p, 0, size_t(words) * 4, ctx->stream));
+        ps->nm = 0;
+    }
+    // ---- the layout, the lowering, the materialised witness ----
+    g->tipset_status.resize(T);
+    std::vector<uint64_t> n_match(T, 0);
+    for (uint32_t t = 0; t < T; ++t) {
+        g->tipset_status[t] = ipcfp_status_t(ps->status[t]);
+        if (ps->nm) n_match[t] = ps->scan.match_off[t + 1] - ps->scan.match_off[t];
+    }
+    g->claim_off.assign(size_t(T) + 1, 0);
+    GenTipsetsLayout lay;
+    if (gen_tipsets_layout(ps->status.data(), n_match.data(), nullptr, T, g->claim_off.data(), nullptr, lay) != kGenLayoutOk)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: 2^32 - 1 or more matches over the chain");
+    if (lay.n_claims != ps->nm) return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: the tipsets' claim ranges do not add up");
+    const uint64_t nm = ps->nm;
+    g->n = nm;
+    ClaimGenPlan plan;
+    rc = claim_gen_plan(ctx, w, ps->scan.matches_p, uint32_t(nm), plan);
+    if (rc) return rc;
+    g->blob_len = plan.total;
+    DevBuf<uint64_t> claim_off_d;
+    DevBuf<long long> epochs_d;
+    std::vector<long long> epochs(2 * size_t(T));
+    if (nm) {
+        for (uint32_t t = 0; t < T; ++t) {
+            epochs[t] = ps->facts[t].parent0_height;
+            epochs[size_t(T) + t] = ps->facts[t].child_height;
+        }
+        IPCFP_HIP(ctx, g->claims_d.alloc(nm));
+        IPCFP_HIP(ctx, g->blob_d.alloc(plan.total + 16));
+        IPCFP_HIP(ctx, claim_off_d.alloc(size_t(T) + 1));
+        IPCFP_HIP(ctx, epochs_d.alloc(2 * size_t(T)));
+        IPCFP_HIP(ctx, hipMemcpyAsync(claim_off_d.p, g->claim_off.data(), (size_t(T) + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        IPCFP_HIP(ctx, hipMemcpyAsync(epochs_d.p, epochs.data(), epochs.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_gen_claim_fill(ctx, witness_view(w), ps->scan.matches_p, ps->msg.p, uint32_t(nm), plan.recs.p, plan.prefix.p, plan.total, 0, 0,
+                                   0u, g->claims_d.p, g->blob_d.p);
+        if (!rc) rc = launch_gent_patch_claims(ctx, g->claims_d.p, uint32_t(nm), claim_off_d.p, T, epochs_d.p, epochs_d.p + T);
+        if (rc) {
+            (void)sync_stream(ctx, ctx->stream);
+            return rc;
+        }
+    }
+    uint64_t nb = 0;
+    g->block_ids.resize(w->n ? w->n : 1);
+    rc = materialize(ctx, w, touched.p, g->block_ids.data(), nullptr, g->block_ids.size(), &nb);  // ONE per chain; synchronises
+    if (rc) {
+        (void)sync_stream(ctx, ctx->stream);
+        return rc;
+    }
+    IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream, true));
+    g->block_ids.resize(nb);
+    if (nm) {
+        if (ps->scan.matches.p == ps->scan.matches_p) {
+            g->matches_d.swap(ps->scan.matches);
+        } else {
+            IPCFP_HIP(ctx, g->matches_d.alloc(nm));
+            IPCFP_HIP(ctx, hipMemcpyAsync(g->matches_d.p, ps->scan.matches_p, nm * sizeof(ipcfp_event_match_t), hipMemcpyDeviceToDevice, ctx->stream));
+            IPCFP_HIP(ctx, sync_stream(ctx, ctx->stream));
+        }
+        g->msg_d.swap(ps->msg);
+    }
     return IPCFP_OK;
 }
 
@@ -502,16 +826,9 @@ int ipcfp_generate_event_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint
     g->ctx = ctx;
     g->n = core.nm;
     // the one tipset the claims name: the key as it was given (a folded slot stays folded)
-    std::memset(&g->tipset, 0, sizeof g->tipset);
-    g->tipset.flags = TC_PARENTS_PARSED | TC_CHILD_PARSED;
-    g->tipset.n_parents = n_parents;
-    std::memcpy(g->tipset.child, child_cid40, IPCFP_CID_SLOT);
-    const uint32_t n_inline = n_parents < uint32_t(IPCFP_MAX_PARENTS) ? n_parents : uint32_t(IPCFP_MAX_PARENTS);
-    if (n_inline) std::memcpy(g->tipset.parents, parent_cids40, size_t(n_inline) * IPCFP_CID_SLOT);
-    if (n_parents > n_inline) {
-        g->more_parents.assign(parent_cids40 + size_t(n_inline) * IPCFP_CID_SLOT, parent_cids40 + size_t(n_parents) * IPCFP_CID_SLOT);
-        g->tipset.more_parents = g->more_parents.data();
-    }
+    generated_set_tipsets(g.get(), parent_cids40, nullptr, n_parents, child_cid40, 1);
+    g->tipset_status.assign(1, IPCFP_ST_TRUE);
+    g->claim_off = {0, core.nm};
     // the lowering: sizes, prefix, then a blob of exactly that length
     ClaimGenPlan plan;
     rc = claim_gen_plan(ctx, w, core.scan.matches.p, uint32_t(core.nm), plan);
@@ -544,13 +861,77 @@ int ipcfp_generate_event_claims(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint
     return IPCFP_OK;
 }
 
+int ipcfp_generate_event_claims_tipsets(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, const uint8_t* parent_cids40, const uint32_t* parent_off,
+                                        const uint8_t* child_cids40, uint32_t n_tipsets, const ipcfp_event_filter_t* filter, int has_actor,
+                                        uint64_t actor, ipcfp_generated_events_t** out) {
+    if (out) *out = nullptr;
+    if (!ctx || !w || w->ctx != ctx || !parent_off || !child_cids40 || !filter || !out || n_tipsets == 0) return IPCFP_E_INVALID;
+    IPCFP_ENTER(ctx);
+    // everything the arguments alone decide, before any device work
+    if (n_tipsets > IPCFP_MAX_GEN_TIPSETS)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: %u tipsets (at most %d)", n_tipsets, IPCFP_MAX_GEN_TIPSETS);
+    uint64_t n_roots = 0;
+    const int args = gen_tipsets_args(parent_off, n_tipsets, &n_roots);
+    if (args == kGenArgsNotAscending) return set_error(ctx, IPCFP_E_INVALID, "generate_event_claims_tipsets: parent_off does not ascend from 0");
+    if (parent_off[n_tipsets] && !parent_cids40) return set_error(ctx, IPCFP_E_INVALID, "generate_event_claims_tipsets: parent slots without parent_cids40");
+    if (w->receipt_lo != 0 || w->receipt_hi != ~0ULL)  // a shard is a cut of ONE tipset
+        return set_error(ctx, IPCFP_E_INVALID, "generate_event_claims_tipsets: the witness has a receipt range set");
+    if (args == kGenArgsTooManyRoots)
+        return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: %llu message-tree roots over the chain (the enumerator orders %u)",
+                         (unsigned long long)n_roots, kGenMaxRoots);
+    for (uint32_t t = 0; t < n_tipsets; ++t)
+        if (parent_off[t + 1] - parent_off[t] > IPCFP_MAX_PARENTS_WIDE)
+            return set_error(ctx, IPCFP_E_UNSUPPORTED, "generate_event_claims_tipsets: tipset %u has a key of %u parent blocks (at most %u)", t,
+                             parent_off[t + 1] - parent_off[t], unsigned(IPCFP_MAX_PARENTS_WIDE));
+    GentChain ch;
+    ch.T = n_tipsets;
+    ch.n_roots = uint32_t(n_roots);
+    ch.n_slots = 2u * n_tipsets + parent_off[n_tipsets];
+    ch.parent_off = parent_off;
+    ch.parents.resize(parent_off[n_tipsets]);
+    ch.children.resize(n_tipsets);
+    ch.seq_tipset.resize(ch.n_roots);
+    for (uint32_t j = 0; j < parent_off[n_tipsets]; ++j) ch.parents[j] = key_from_slot(parent_cids40 + size_t(j) * IPCFP_CID_SLOT);
+    for (uint32_t t = 0; t < n_tipsets; ++t) {
+        ch.children[t] = key_from_slot(child_cids40 + size_t(t) * IPCFP_CID_SLOT);
+        for (uint32_t r = 2u * parent_off[t]; r < 2u * parent_off[t + 1]; ++r) ch.seq_tipset[r] = t;
+    }
+    std::unique_ptr<ipcfp_generated_events, void (*)(ipcfp_generated_events*)> g(new (std::nothrow) ipcfp_generated_events(),
+                                                                                ipcfp_generated_events_destroy);
+    if (!g) return set_error(ctx, IPCFP_E_NOMEM, "generate_event_claims_tipsets: out of memory");
+    g->ctx = ctx;
+    generated_set_tipsets(g.get(), parent_cids40, parent_off, 0, child_cids40, n_tipsets);
+    const int rc = generate_events_tipsets_body(ctx, w, ch, filter, has_actor, actor, g.get());
+    const hipError_t e = sync_stream(ctx, ctx->stream);  // (queued work reads buffers of this frame, on every path)
+    if (rc) return rc;
+    IPCFP_HIP(ctx, e);
+    ctl_preprime(ctx);
+    *out = g.release();
+    return IPCFP_OK;
+}
+
 void ipcfp_generated_events_destroy(ipcfp_generated_events_t* g) {
     if (!g) return;
     if (g->unpacked) ipcfp_unpacked_events_destroy(g->unpacked);
     delete g;
 }
 uint64_t ipcfp_generated_events_count(const ipcfp_generated_events_t* g) { return g ? g->n : 0; }
-const ipcfp_tipset_ref_t* ipcfp_generated_events_tipset(const ipcfp_generated_events_t* g) { return g ? &g->tipset : nullptr; }
+const ipcfp_tipset_ref_t* ipcfp_generated_events_tipset(const ipcfp_generated_events_t* g) {
+    return g && !g->tipsets.empty() ? g->tipsets.data() : nullptr;
+}
+uint32_t ipcfp_generated_events_tipset_count(const ipcfp_generated_events_t* g) { return g ? uint32_t(g->tipsets.size()) : 0u; }
+const ipcfp_tipset_ref_t* ipcfp_generated_events_tipsets(const ipcfp_generated_events_t* g, uint32_t* n) {
+    if (n) *n = g ? uint32_t(g->tipsets.size()) : 0u;
+    return g ? g->tipsets.data() : nullptr;
+}
+const ipcfp_status_t* ipcfp_generated_events_tipset_status(const ipcfp_generated_events_t* g, uint32_t* n) {
+    if (n) *n = g ? uint32_t(g->tipset_status.size()) : 0u;
+    return g ? g->tipset_status.data() : nullptr;
+}
+const uint64_t* ipcfp_generated_events_tipset_claim_off(const ipcfp_generated_events_t* g, uint32_t* n) {
+    if (n) *n = g ? uint32_t(g->tipsets.size()) : 0u;  // (n_tipsets: the array holds *n + 1 offsets)
+    return g ? g->claim_off.data() : nullptr;
+}
 const void* ipcfp_generated_events_claims_device(const ipcfp_generated_events_t* g) { return g ? g->claims_d.p : nullptr; }
 const void* ipcfp_generated_events_blob_device(const ipcfp_generated_events_t* g, uint64_t* blob_len) {
     if (blob_len) *blob_len = g ? g->blob_len : 0;
@@ -590,7 +971,7 @@ int ipcfp_generated_events_proofs(ipcfp_generated_events_t* g, const ipcfp_event
     if (!g->unpacked) {
         if (const int rc = generated_host_copy(g)) return rc;
         uint64_t bad = ~0ull;
-        const int rc = ipcfp_unpack_event_claims(&g->tipset, 1, g->claims_h.data(), g->n, g->blob_h.data(), g->blob_len, &g->unpacked, &bad);
+        const int rc = ipcfp_unpack_event_claims(g->tipsets.data(), g->tipsets.size(), g->claims_h.data(), g->n, g->blob_h.data(), g->blob_len, &g->unpacked, &bad);
         if (bad_index) *bad_index = bad;
         if (rc == IPCFP_E_UNSUPPORTED)
             return set_error(g->ctx, rc, "generated_events_proofs: a CID of proof %llu is longer than the %d-byte slot and the claim keeps only its fold",

@@ -39,7 +39,7 @@ struct TipsetsHost {
 
 int scan_tipsets_body(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* roots40, uint32_t T, const ipcfp_event_filter_t* filters,
                       const uint8_t* has_actor, const uint64_t* actors, uint32_t n_specs, uint32_t* touched_d, TipsetsScanResult& out,
-                      uint64_t cap_receipts, uint64_t cap_matches, TipsetsHost& host) {
+                      uint64_t cap_receipts, uint64_t cap_matches, TipsetsHost& host, const uint8_t* skip_mask) {
     const WitnessView view = witness_view(w);
     // the block-order event parse starts now (no filter: no per-block counts), beside the enumeration
     int rc = block_table_prefetch(ctx, w, nullptr, 0, 0);
@@ -58,6 +58,7 @@ int scan_tipsets_body(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* roots40, 
     for (uint32_t t = 0; t < T; ++t) {
         host.specs[t].root = key_from_slot(roots40 + size_t(t) * IPCFP_CID_SLOT);
         host.specs[t].seq = t;
+        if (skip_mask && skip_mask[t]) host.specs[t].skip = 1;  // the caller's: status ERR, phase 0, nothing walked or recorded
     }
     DevBuf<AmtRootSpec> roots;
     DevBuf<unsigned long long> enum_err;
@@ -188,12 +189,13 @@ int scan_tipsets_body(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* roots40, 
 
 int scan_events_tipsets_device(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* roots40, uint32_t n_tipsets,
                                const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors, uint32_t n_specs,
-                               uint32_t* touched_d, TipsetsScanResult& out, uint64_t cap_receipts, uint64_t cap_matches) {
+                               uint32_t* touched_d, TipsetsScanResult& out, uint64_t cap_receipts, uint64_t cap_matches,
+                               const uint8_t* skip_mask) {
     // The body's copies read and write `host`, and its kernels read buffers that go back to the pool when it returns: the
     // stream is drained before either goes away, on every path (an error included), as scan_events_multi_device does.
     TipsetsHost host;
     const int rc = scan_tipsets_body(ctx, w, roots40, n_tipsets, filters, has_actor, actors, n_specs, touched_d, out, cap_receipts,
-                                     cap_matches, host);
+                                     cap_matches, host, skip_mask);
     const hipError_t e = sync_stream(ctx, ctx->stream);
     if (rc) return rc;
     IPCFP_HIP(ctx, e);

@@ -28,9 +28,12 @@ struct TipsetsScanResult {
 };
 
 // One enumeration of the n_tipsets receipts trees (one more per failing tree), PASS 1, prefix sum, PASS 2.  `touched_d`
-// (nullable, device) is OR-ed into.  The stream is drained when it returns.
+// (nullable, device) is OR-ed into.  The stream is drained when it returns.  `skip_mask` (nullable, n_tipsets bytes): a tipset
+// whose byte is set is not looked at — its root is never loaded, its ranges are empty, its status stays IPCFP_ST_ERR with
+// phase 0 (the chain generator's tipsets that failed before the scan, host/generate.cpp).
 int scan_events_tipsets_device(ipcfp_ctx* ctx, ipcfp_witness* w, const uint8_t* roots40, uint32_t n_tipsets,
                                const ipcfp_event_filter_t* filters, const uint8_t* has_actor, const uint64_t* actors, uint32_t n_specs,
-                               uint32_t* touched_d, TipsetsScanResult& out, uint64_t cap_receipts, uint64_t cap_matches);
+                               uint32_t* touched_d, TipsetsScanResult& out, uint64_t cap_receipts, uint64_t cap_matches,
+                               const uint8_t* skip_mask = nullptr);
 
 }  // namespace ipcfp

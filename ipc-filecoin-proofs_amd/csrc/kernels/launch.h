@@ -320,6 +320,32 @@ int launch_sgent_cut_count(ipcfp_ctx* ctx, const uint32_t* rows_d, uint32_t n_ti
 int launch_sgent_cut_fill(ipcfp_ctx* ctx, const uint32_t* mask_d, const uint32_t* offset_d, const uint64_t* total_d, uint32_t n_tipsets,
                           const uint32_t* union_ids_d, uint32_t n_union, uint64_t cap, uint32_t* ids_out_d, uint64_t* tipset_off_d);
 
+// --- event_gen_tipsets.inc (part of tipset_prepare_general.hip) --- generate_event_proof for a CHAIN of tipset pairs
+// (ipcfp_generate_event_claims_tipsets, host/generate.cpp).  tips_d: GentTipset[n_tipsets], facts_d: GentFacts[n_tipsets]
+// (host/generate.cpp mirrors both records); `w` of a kernel that fetches blocks: the RECORDING view.
+// the chain prologue: ctxs_d TipsetCtxDev[n_tipsets] (inputs set), n_slots = Σ (2 + n_parents) workgroups; roots_d: Σ 2·n_parents
+// specs with seq = their number in the chain; err_d[n_tipsets] (kNoEnumError each): stage 1's error word per tipset
+int launch_gent_prologue(ipcfp_ctx* ctx, const WitnessView& w, void* ctxs_d, const void* tips_d, uint32_t n_tipsets, uint32_t n_slots,
+                         AmtRootSpec* roots_d, unsigned long long* err_d, void* facts_d);
+int launch_gent_skip_roots(ipcfp_ctx* ctx, AmtRootSpec* roots_d, uint32_t lo, uint32_t hi);
+// leaves → keys_d[n], tip_d[n] (seq_tipset_d: root number → tipset), then the one-probe first-occurrence flags of (tipset, CID)
+// (slots_d: mask + 1 words of 0xff, first_d: n zeroed words)
+int launch_gent_exec_order(ipcfp_ctx* ctx, const WitnessView& w, const LeafRef* leaves_d, uint32_t n, const uint32_t* seq_tipset_d,
+                           uint32_t n_roots, CidKey* keys_d, uint32_t* tip_d, unsigned long long* slots_d, uint32_t mask,
+                           uint32_t* first_d);
+// behind launch_scan_u32 over the flags: exec_off_d[n_tipsets + 1]; first_by_root_d: launch_tipset_bounds over the root numbers
+int launch_gent_exec_ranges(ipcfp_ctx* ctx, const void* tips_d, uint32_t n_tipsets, const uint32_t* first_by_root_d, const uint32_t* pos_d,
+                            const uint64_t* total_d, uint32_t n, uint32_t* exec_off_d);
+// msg_d[k] = list_d[exec_off[t] + exec_index] for match k of tipset t (match_off_d: n_tipsets + 1); oor_d[t] |= 1 when outside
+int launch_gent_gather(ipcfp_ctx* ctx, const void* matches_d, uint32_t n, const uint64_t* match_off_d, uint32_t n_tipsets,
+                       const uint32_t* exec_off_d, const CidKey* list_d, CidKey* msg_d, uint32_t* oor_d);
+// launch_mark_cids with missing_d[key_tip_d[i]] |= 1
+int launch_gent_mark_base(ipcfp_ctx* ctx, const WitnessView& w, const CidKey* keys_d, const uint32_t* key_tip_d, uint32_t n,
+                          uint32_t* missing_d);
+// claim k of tipset t (claim_off_d: n_tipsets + 1): tipset = t and the tipset's two epochs
+int launch_gent_patch_claims(ipcfp_ctx* ctx, void* claims_d, uint32_t n, const uint64_t* claim_off_d, uint32_t n_tipsets,
+                             const long long* parent_epoch_d, const long long* child_epoch_d);
+
 // --- shard.hip ---
 int launch_plan_receipts(ipcfp_ctx* ctx, const WitnessView& rec, const CidKey& receipts_root, uint64_t lo, uint32_t n);
 int launch_plan_receipts_all(ipcfp_ctx* ctx, const WitnessView& rec, const CidKey& receipts_root, uint32_t n,

@@ -164,3 +164,5 @@ int launch_tipset_prepare(ipcfp_ctx* ctx, const WitnessView& w, const void* jobs
 }
 
 }  // namespace ipcfp
+
+#include "event_gen_tipsets.inc"
