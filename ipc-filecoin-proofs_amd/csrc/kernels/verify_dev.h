@@ -111,6 +111,54 @@ __device__ __forceinline__ uint32_t verify_event_prefix(const EventClaimPacked& 
     return IPCFP_ST_TRUE;
 }
 
+// What steps 1-3 and the table lookup read of a context, as one value: a kernel whose context is uniform over the
+// wavefront reads it with ONE group of scalar loads and one wait (k_verify_events_table's usual claim), where the ladder
+// above reads a field per rung.
+struct EventCtxFacts {
+    uint32_t flags, n_parents, child_status, parents_match, parent0_status, exec_status;
+    long long child_height, parent0_height;
+    const CidKey* exec_keys;
+    const uint32_t* exec_inv;
+    uint64_t exec_len;
+    bool has_receipt_table;  // receipt_leaves && receipt_recs
+    uint64_t n_receipt_leaves, receipt_first;
+    const ReceiptRec* receipt_recs;
+    const EventRec* event_recs;
+};
+
+__device__ __forceinline__ EventCtxFacts event_ctx_facts(const TipsetCtxDev& tc) {
+    return EventCtxFacts{tc.flags,        tc.n_parents,      tc.child_status, tc.parents_match,
+                         tc.parent0_status, tc.exec_status,  tc.child_height, tc.parent0_height,
+                         tc.exec_keys,    tc.exec_inv,       tc.exec_len,     tc.receipt_leaves != nullptr && tc.receipt_recs != nullptr,
+                         tc.n_receipt_leaves, tc.receipt_first, tc.receipt_recs, tc.event_recs};
+}
+
+// One rung of a ladder whose verdicts are taken from registers: the FIRST failing rung's status stands, nothing returns.
+struct Verdict {
+    uint32_t st = IPCFP_ST_TRUE;
+    bool settled = false;
+    __device__ __forceinline__ void rung(bool fails, uint32_t status) {
+        st = (!settled && fails) ? status : st;
+        settled = settled || fails;
+    }
+};
+
+// verify_event_prefix's rungs up to the execution-order compare (its lines, in its order), from the facts
+__device__ __forceinline__ void event_prefix_rungs(Verdict& v, const EventClaimPacked& c, const EventCtxFacts& f,
+                                                   const ipcfp_trust_policy_t& trust) {
+    v.rung(!(f.flags & TC_PARENTS_PARSED) || !(f.flags & TC_CHILD_PARSED), IPCFP_ST_ERR_BAD_CLAIM);          // :130-131
+    v.rung(!ev_trusted(trust, c.parent_epoch), IPCFP_ST_FALSE_UNTRUSTED_PARENT);                               // :134
+    v.rung(!ev_trusted(trust, c.child_epoch), IPCFP_ST_FALSE_UNTRUSTED_CHILD);                                 // :139
+    v.rung(f.child_status != IPCFP_ST_TRUE, f.child_status);                                                   // :155-158
+    v.rung(!f.parents_match, IPCFP_ST_FALSE_PARENTS_MISMATCH);                                                 // :161
+    v.rung(f.child_height != c.child_epoch, IPCFP_ST_FALSE_CHILD_EPOCH);                                       // :166
+    v.rung(f.n_parents == 0, IPCFP_ST_ERR_EMPTY_PARENTS);                                                      // :172 (panic)
+    v.rung(f.parent0_status != IPCFP_ST_TRUE, f.parent0_status);                                               // :171-174
+    v.rung(f.parent0_height != c.parent_epoch, IPCFP_ST_FALSE_PARENT_EPOCH);                                   // :176
+    v.rung(f.exec_status != IPCFP_ST_TRUE, f.exec_status);                                                     // :190
+    v.rung(!(c.flags & EC_MSG_PARSED), IPCFP_ST_ERR_BAD_CLAIM);                                                // :193
+}
+
 // Step 4 (verify_receipt_and_event, :207-254) when the receipt was enumerated and its events tabulated: what
 // `Amt::load(events_root)`, `get(event_index)`, extract_evm_log and the compares observe is all in the records.
 // `settled` = false: the table does not cover this claim (receipt outside the enumeration, RK_WALK) — nothing decided.

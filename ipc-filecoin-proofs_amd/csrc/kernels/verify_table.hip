@@ -1,9 +1,16 @@
 // csrc/kernels/verify_table.hip — `verify_single_proof` (src/proofs/events/verifier.rs:92-290) for the claims whose
 // receipt was enumerated and whose events are tabulated (event_table.h): steps 1-3 are table lookups (execution-order
 // hash table), step 4 compares the claim with bytes at addresses the records name.  No block is parsed here, so the
-// kernel needs neither the CBOR reader nor LDS and runs at full occupancy; a claim the table does not cover is
-// marked kStPending and taken by the general walker (k_verify_events) right behind.
+// kernel needs no CBOR reader; a claim the table does not cover is marked kStPending and taken by the general walker
+// (k_verify_events) right behind.
+//
+// The usual claim (verify_table_hot) is four batches of loads, each issued whole before any of it is waited for, and
+// then a ladder of selects over registers: neither LDS nor scratch.  Every other claim keeps the ladder of early
+// returns (verify_table_one), whose dynamically indexed EventRec the compiler keeps in LDS (64 bytes a lane: 16 KB a
+// workgroup, touched by those claims only) — DESIGN.md §31.
 #include <hip/hip_runtime.h>
+
+#include <cstddef>
 
 #include "../common.h"
 #include "launch.h"
@@ -117,6 +124,143 @@ __device__ __forceinline__ uint32_t verify_table_one(const WitnessView& w, const
     return verify_event_record_batched(w, c, e, p, blob, filter, has_filter);
 }
 
+// ---- the usual claim: four load batches, then the verdicts -----------------------------------------------------------
+// A claim is "usual" when its wavefront names one context, it claims at most two topics, and its data is 32 bytes or can
+// never match: then everything the reference's ladder looks at sits behind a chain of loads FOUR deep,
+//   A  the claim
+//   B  the claimed bytes in the blob, receipt_recs[exec_index - receipt_first], exec_inv[exec_index], the context's facts
+//   C  event_recs[first + popcount], exec_keys[inv], (w.off[block] when locations are wanted)
+//   D  the event's topics and data
+// and the ladder itself needs no load at all.  Written rung by rung with early returns (verify_table_one) hipcc puts a
+// branch and a full wait around nearly every load — seven vector-memory waits and some twenty scalar ones on an honest
+// claim.  Here every batch is issued whole, the rungs are selects, and the first failing rung's status stands.
+//
+// A load whose guard is false reads `safe` (the lane's own claim: 104 readable bytes already in cache) instead of
+// branching: never an out-of-bounds index, never a null table.  Every address the ladder of early returns would not
+// have formed is guarded off, so this path dereferences a subset of what verify_table_one does.
+// (Global address space by name: a table pointer read out of a context is generic to the compiler, and a select between
+// it and `safe` would make every one of these a flat load.)
+typedef const __attribute__((address_space(1))) uint8_t* gbytes_t;
+__device__ __forceinline__ gbytes_t guarded(bool ok, const void* p, const void* safe) {
+    return ok ? (gbytes_t)p : (gbytes_t)safe;
+}
+__device__ __forceinline__ u64x2_t ld16(gbytes_t p) {
+    u64x2_t v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+}
+// The end of a batch: the values are waited for HERE, by every lane.  Without it hipcc sinks a load whose result only
+// some lanes use into a branch of those lanes and waits for it there, alone — one more link in the chain.
+__device__ __forceinline__ void batch_end(uint64_t a, uint64_t b = 0, uint64_t c = 0, uint64_t d = 0, uint64_t e = 0) {
+    asm volatile("" ::"v"(a), "v"(b), "v"(c), "v"(d), "v"(e));
+}
+
+static_assert(offsetof(ReceiptRec, first) == 4 && offsetof(ReceiptRec, bitmap) == 8 && offsetof(ReceiptRec, block) == 16,
+              "verify_table_hot reads a ReceiptRec as three words");
+static_assert(offsetof(EventRec, topic_rel) == 16 && offsetof(EventRec, data_rel) == 24 && offsetof(EventRec, ev_len) == 26 &&
+                  offsetof(EventRec, data_len) == 28,
+              "verify_table_hot reads an EventRec as four words");
+
+__device__ __forceinline__ bool hot_shape(const EventClaimPacked& c) {
+    return c.n_topics <= 2 && (!(c.flags & EC_DATA_MATCHABLE) || c.data_len == 32);
+}
+
+// `cold` = true: not decided here (the execution-order compare failed, so the hash table has to be asked; or a record
+// kind the table does not define) — the caller runs verify_table_one, and `loc` is to be ignored.
+__device__ __forceinline__ uint32_t verify_table_hot(const WitnessView& w, const EventClaimPacked& c, const TipsetCtxDev& tc,
+                                                     const uint8_t* __restrict__ blob, const ipcfp_trust_policy_t& trust,
+                                                     const ipcfp_event_filter_t& filter, bool has_filter, bool want_where,
+                                                     const void* safe, ValueLoc& loc, bool& cold) {
+    // ---- batch B: what the claim and the context's pointers address
+    const EventCtxFacts f = event_ctx_facts(tc);
+    Verdict v;
+    event_prefix_rungs(v, c, f, trust);  // (registers only: the claim and the facts)
+    const bool pre_ok = !v.settled;
+    // (the two records that batch C hangs on go first: vmcnt counts in order, so they are waited for without the blob)
+    const bool tabulated = f.has_receipt_table && c.exec_index >= f.receipt_first && c.exec_index - f.receipt_first < f.n_receipt_leaves;
+    uint64_t rw[3];  // the ReceiptRec as words
+    __builtin_memcpy(rw, guarded(tabulated, f.receipt_recs + (c.exec_index - f.receipt_first), safe), 24);
+    const bool inv_ok = pre_ok && f.exec_inv && f.exec_keys && c.exec_index < f.exec_len;
+    uint32_t inv;
+    __builtin_memcpy(&inv, guarded(inv_ok, f.exec_inv + c.exec_index, safe), 4);
+    const bool matchable = (c.flags & EC_DATA_MATCHABLE) != 0;  // hot_shape: then data_len == 32
+    const gbytes_t q0 = guarded(c.n_topics >= 1, blob + c.topics_off, safe);
+    const gbytes_t q1 = guarded(c.n_topics == 2, blob + c.topics_off + 33, safe);
+    const gbytes_t qd = guarded(matchable, blob + c.data_off, safe);
+    ClaimedBytes p;
+    p.flag[0] = q0[0];
+    p.topic[0][0] = ld16(q0 + 1);
+    p.topic[0][1] = ld16(q0 + 17);
+    p.flag[1] = q1[0];
+    p.topic[1][0] = ld16(q1 + 1);
+    p.topic[1][1] = ld16(q1 + 17);
+    p.data[0] = ld16(qd);
+    p.data[1] = ld16(qd + 16);
+    batch_end(rw[0], rw[1], rw[2], inv);
+    const uint32_t rr_kind = uint32_t(rw[0]), rr_first = uint32_t(rw[0] >> 32), rr_block = uint32_t(rw[2]);
+    const uint64_t rr_bitmap = rw[1];
+
+    // ---- batch C: what the receipt record and the inverse order address
+    CidKey key;
+    __builtin_memcpy(&key, guarded(inv_ok, f.exec_keys + inv, safe), 40);
+    const uint32_t bit = uint32_t(c.event_index) & 63u;
+    const bool present = c.event_index < 64 && ((rr_bitmap >> bit) & 1ull);
+    const bool have_event = pre_ok && tabulated && rr_kind == RK_TABLE && f.event_recs && present;
+    const uint32_t slot = rr_first + uint32_t(__popcll(rr_bitmap & ((1ull << bit) - 1ull)));
+    uint64_t ew[4];  // the EventRec as words: no field is ever indexed dynamically
+    __builtin_memcpy(ew, guarded(have_event, f.event_recs + slot, safe), 32);
+    uint64_t block_off;
+    __builtin_memcpy(&block_off, guarded(want_where && have_event, w.off + rr_block, safe), 8);
+    batch_end(key.w[0], key.w[1], key.w[2], key.w[3], key.w[4]);
+    batch_end(ew[0], ew[1], ew[2], ew[3], block_off);
+
+    // steps 1-3 end: `exec_order.iter().position(|c| c == msg)` == exec_index (verify_event_prefix)
+    const bool exec_ok = inv_ok && cid_equal(key, c.message);
+    // verify_event_from_table (verify_dev.h), same rules in the same order
+    v.rung(!tabulated || rr_kind == RK_WALK, kStPending);
+    v.rung(rr_kind == RK_NO_EVENTS, IPCFP_ST_FALSE_NO_EVENTS_ROOT);                                           // :229
+    v.rung(rr_kind >= 64, rr_kind);                                                                           // :234 Err
+    v.rung(c.event_index == ~0ULL, IPCFP_ST_ERR);                                                             // > MAX_INDEX
+    v.rung(!present, IPCFP_ST_FALSE_NO_EVENT);                                                                // :237
+    const bool reached = !v.settled;  // the proof has reached its event
+    cold = pre_ok && (!exec_ok || (reached && !have_event));
+
+    // verify_event_record_batched, same rules in the same order
+    const uint64_t base_flags = ew[0], e_emitter = ew[1];
+    const uint32_t rel0 = uint32_t(ew[2]) & 0xffffu, rel1_b = uint32_t(ew[2] >> 16) & 0xffffu;
+    const uint32_t data_rel = uint32_t(ew[3]) & 0xffffu, ev_len = uint32_t(ew[3] >> 16) & 0xffffu, e_data_len = uint32_t(ew[3] >> 32);
+    v.rung(e_emitter != c.emitter, IPCFP_ST_FALSE_EMITTER);                                                   // :262
+    v.rung(!(base_flags & kEvIsLog), IPCFP_ST_FALSE_NOT_EVM_LOG);                                             // :267
+    const uint32_t nt = uint32_t(base_flags >> kEvTopicShift) & 0xffu;
+    v.rung(nt != c.n_topics, IPCFP_ST_FALSE_TOPIC_COUNT);                                                     // :272
+
+    // ---- batch D: the event's bytes (only where the ladder of early returns reads them too)
+    const bool bytes_wanted = have_event && exec_ok && !v.settled;  // hence nt == c.n_topics <= 2
+    const uint8_t* item = w.arena + (base_flags & kEvBaseMask);
+    const uint32_t rel1 = (base_flags & kEvCaseA) ? rel0 + 32u : rel1_b;
+    const bool data_shape = matchable && c.data_len == e_data_len;
+    const gbytes_t a0 = guarded(bytes_wanted && nt >= 1, item + rel0, safe);
+    const gbytes_t a1 = guarded(bytes_wanted && nt == 2, item + rel1, safe);
+    const gbytes_t ad = guarded(bytes_wanted && data_shape, item + data_rel, safe);
+    const u64x2_t t0[2] = {ld16(a0), ld16(a0 + 16)}, t1[2] = {ld16(a1), ld16(a1 + 16)}, d[2] = {ld16(ad), ld16(ad + 16)};
+
+    v.rung(nt >= 1 && (!p.flag[0] || differ32(p.topic[0], t0)), IPCFP_ST_FALSE_TOPIC);                        // :276-281
+    v.rung(nt == 2 && (!p.flag[1] || differ32(p.topic[1], t1)), IPCFP_ST_FALSE_TOPIC);
+    v.rung(!data_shape, IPCFP_ST_FALSE_DATA);                                                                 // :284-287
+    v.rung(differ32(p.data, d), IPCFP_ST_FALSE_DATA);
+    u64x2_t f0[2], f1[2];
+    __builtin_memcpy(f0, filter.topic0, 32);
+    __builtin_memcpy(f1, filter.topic1, 32);
+    v.rung(has_filter && nt < 2, IPCFP_ST_FALSE_FILTER);                                                      // :247-251
+    v.rung(has_filter && (differ32(t0, f0) || differ32(t1, f1)), IPCFP_ST_FALSE_FILTER);
+
+    const bool located = reached && have_event;
+    loc.block = located ? rr_block : kNoBlock;
+    loc.off = located ? uint32_t((base_flags & kEvBaseMask) - block_off) : 0u;
+    loc.len = located ? ev_len : 0u;
+    return v.st;
+}
+
 __global__ __launch_bounds__(256) void k_verify_events_table(WitnessView w, const EventClaimPacked* __restrict__ claims, uint32_t n,
                                                              const TipsetCtxDev* __restrict__ ctxs, uint32_t n_ctxs,
                                                              const uint8_t* __restrict__ blob, uint64_t blob_len,
@@ -134,10 +278,33 @@ __global__ __launch_bounds__(256) void k_verify_events_table(WitnessView w, cons
     // The proofs of a wavefront nearly always name ONE tipset pair: its context (≈700 bytes of header facts and
     // table pointers) is then read through the scalar unit once per wavefront instead of by 64 lanes apiece.
     const uint32_t ctx0 = __builtin_amdgcn_readfirstlane(inb ? c.context : 0xffffffffu);
-    if (__all(!inb || c.context == ctx0)) {
-        if (inb) st = verify_table_one(w, c, ctxs[ctx0], blob, trust, filter, has_filter != 0, where ? &loc : nullptr);
-    } else if (inb) {
-        st = verify_table_one(w, c, ctxs[c.context], blob, trust, filter, has_filter != 0, where ? &loc : nullptr);
+    bool cold = inb;  // lanes that take the ladder of early returns
+    if (ctx0 != 0xffffffffu && __all(!inb || c.context == ctx0)) {
+        if (inb && hot_shape(c)) {
+            ValueLoc hot_loc;
+            bool again;
+            const uint32_t hot_st = verify_table_hot(w, c, ctxs[ctx0], blob, trust, filter, has_filter != 0, where != nullptr,
+                                                     claims + t, hot_loc, again);
+            st = again ? st : hot_st;
+            loc.block = again ? loc.block : hot_loc.block;
+            loc.off = again ? loc.off : hot_loc.off;
+            loc.len = again ? loc.len : hot_loc.len;
+            cold = again;
+        }
+    }
+    // Everything else — a claim that needs the hash-table probe, more than two topics, data of another length, contexts
+    // that differ within the wavefront — takes the ladder of early returns (verify_table_one), each lane with its own context.
+    // (They read their claim AGAIN, through a pointer the compiler cannot tell from another: kept in registers for them,
+    // the claim's 26 words would be live across the whole hot path and cost it a wavefront of occupancy.)
+    if (__any(cold)) {
+        if (cold) {
+            const EventClaimPacked* mine = claims + t;
+            asm volatile("" : "+v"(mine));
+            const EventClaimPacked cc = *mine;
+            ValueLoc cold_loc{kNoBlock, 0, 0};
+            st = verify_table_one(w, cc, ctxs[cc.context], blob, trust, filter, has_filter != 0, &cold_loc);
+            loc = cold_loc;
+        }
     }
     if (!live) return;
     status[t] = uint8_t(st);
