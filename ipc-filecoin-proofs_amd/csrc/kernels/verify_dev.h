@@ -66,10 +66,13 @@ __device__ __forceinline__ uint32_t verify_event_record(const WitnessView& w, co
     if (nt != c.n_topics) return IPCFP_ST_FALSE_TOPIC_COUNT;                                                  // :272
     const uint8_t* item = w.arena + (e.base_flags & kEvBaseMask);
     const bool case_a = (e.base_flags & kEvCaseA) != 0;
+    // (the four offsets as one word, picked by a shift: indexed dynamically, the record would live in LDS or scratch)
+    const uint64_t rels = uint64_t(e.topic_rel[0]) | uint64_t(e.topic_rel[1]) << 16 | uint64_t(e.topic_rel[2]) << 32 |
+                          uint64_t(e.topic_rel[3]) << 48;
     for (uint32_t i = 0; i < nt; ++i) {                                                                       // :276-281
         const uint8_t* claimed = blob + c.topics_off + 33u * i;
         if (!claimed[0]) return IPCFP_ST_FALSE_TOPIC;  // the claimed string is not "0x" + 64 hex digits
-        const uint32_t rel = case_a ? uint32_t(e.topic_rel[0]) + 32u * i : uint32_t(e.topic_rel[i & 3u]);
+        const uint32_t rel = case_a ? uint32_t(e.topic_rel[0]) + 32u * i : uint32_t(rels >> (16u * (i & 3u))) & 0xffffu;
         if (!bytes_equal_global(item + rel, claimed + 1, 32)) return IPCFP_ST_FALSE_TOPIC;
     }
     if (!(c.flags & EC_DATA_MATCHABLE) || c.data_len != e.data_len) return IPCFP_ST_FALSE_DATA;               // :284-287

@@ -5,9 +5,9 @@
 // (k_verify_events) right behind.
 //
 // The usual claim (verify_table_hot) is four batches of loads, each issued whole before any of it is waited for, and
-// then a ladder of selects over registers: neither LDS nor scratch.  Every other claim keeps the ladder of early
-// returns (verify_table_one), whose dynamically indexed EventRec the compiler keeps in LDS (64 bytes a lane: 16 KB a
-// workgroup, touched by those claims only) — DESIGN.md §31.
+// then a ladder of selects over registers.  Every other claim keeps the ladder of early returns (verify_table_one) —
+// DESIGN.md §31.  What a wavefront reads of contiguous memory — its claims, and the window of the blob its usual claims
+// name — it reads coalesced through an LDS region of its own.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -15,6 +15,7 @@
 #include "../common.h"
 #include "launch.h"
 #include "verify_dev.h"
+#include "verify_window.h"
 
 namespace ipcfp {
 
@@ -135,8 +136,8 @@ __device__ __forceinline__ uint32_t verify_table_one(const WitnessView& w, const
 // branch and a full wait around nearly every load — seven vector-memory waits and some twenty scalar ones on an honest
 // claim.  Here every batch is issued whole, the rungs are selects, and the first failing rung's status stands.
 //
-// A load whose guard is false reads `safe` (the lane's own claim: 104 readable bytes already in cache) instead of
-// branching: never an out-of-bounds index, never a null table.  Every address the ladder of early returns would not
+// A load whose guard is false reads `safe` (the wavefront's first claim: 104 readable bytes, one line for all 64 lanes)
+// instead of branching: never an out-of-bounds index, never a null table.  Every address the ladder of early returns would not
 // have formed is guarded off, so this path dereferences a subset of what verify_table_one does.
 // (Global address space by name: a table pointer read out of a context is generic to the compiler, and a select between
 // it and `safe` would make every one of these a flat load.)
@@ -165,37 +166,118 @@ __device__ __forceinline__ bool hot_shape(const EventClaimPacked& c) {
     return c.n_topics <= 2 && (!(c.flags & EC_DATA_MATCHABLE) || c.data_len == 32);
 }
 
+// ---- a wavefront's LDS region ------------------------------------------------------------------------------------------
+// The claims of a wavefront are contiguous (64 × 104 bytes), and so, nearly always, are the blob entries they name.  Read
+// lane by lane, one load instruction touches some fifty 128-byte lines; read as ONE byte range, 16 bytes a lane, it touches
+// eight, each once.  So every wavefront copies its claims into an LDS region of its own and every lane takes its claim
+// from there; the region then takes the WINDOW of the blob (verify_window.h) and the usual claims take their claimed
+// bytes from it.  A region belongs to one wavefront: a wavefront's LDS instructions execute in order, so a fence and the
+// wavefront barrier between the writes and the reads are all the ordering there is — nothing waits for another wavefront.
+constexpr uint32_t kStageStride = kVerifyWindowBytes + 16u;  // (+16: the ninth word of a 32-byte piece that ends the window)
+constexpr uint32_t kStageLoads = (kVerifyWindowBytes + 1023u) / 1024u;
+
+// `bytes` <= kVerifyWindowBytes from src (any alignment) to the region: whole 16-byte pieces, all loads in flight before
+// the first write, then the odd bytes one lane apiece.  Reads [src, src + bytes) and nothing else.
+__device__ __forceinline__ void stage_copy(uint8_t* __restrict__ region, const uint8_t* __restrict__ src, uint32_t bytes, uint32_t lane) {
+    const uint32_t whole = bytes & ~15u;
+    u64x2_t v[kStageLoads];
+#pragma unroll
+    for (uint32_t k = 0; k < kStageLoads; ++k) {
+        const uint32_t o = (k * 64u + lane) * 16u;
+        v[k] = u64x2_t{0, 0};
+        if (o < whole) v[k] = ld16(src + o);
+    }
+    // (every access to a region is a memcpy: bytes to the compiler, which then keeps reads and writes of it in order)
+#pragma unroll
+    for (uint32_t k = 0; k < kStageLoads; ++k) {
+        const uint32_t o = (k * 64u + lane) * 16u;
+        if (o < whole) __builtin_memcpy(__builtin_assume_aligned(region + o, 16), &v[k], 16);  // ds_write_b128
+    }
+    if (whole + lane < bytes) region[whole + lane] = src[whole + lane];
+}
+__device__ __forceinline__ void stage_publish() {  // the region's writes before its reads, within the wavefront
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// 32 bytes at byte j of the region: nine aligned words and a byte shift (a 64- or 128-bit LDS read off its natural
+// alignment is replayed, some 64 cycles each; a 32-bit one is not)
+__device__ __forceinline__ void region_ld32(const uint8_t* region, uint32_t j, u64x2_t out[2]) {
+    const uint8_t* p = static_cast<const uint8_t*>(__builtin_assume_aligned(region + (j & ~3u), 4));
+    const uint32_t s = j & 3u;
+    uint32_t x[9], a[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) __builtin_memcpy(&x[i], p + 4 * i, 4);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) a[i] = __builtin_amdgcn_alignbyte(x[i + 1], x[i], s);
+    out[0] = u64x2_t{a[0] | uint64_t(a[1]) << 32, a[2] | uint64_t(a[3]) << 32};
+    out[1] = u64x2_t{a[4] | uint64_t(a[5]) << 32, a[6] | uint64_t(a[7]) << 32};
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = min(v, uint32_t(__shfl_xor(v, m, 64)));
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, uint32_t(__shfl_xor(v, m, 64)));
+    return v;
+}
+
+// Called by EVERY lane of a wavefront whose in-bounds claims name one context; `hot`: this lane holds a usual claim (in
+// bounds, hot_shape).  The other lanes only help to carry the window: each of their loads is guarded off, their result
+// is to be ignored.  `region`: the wavefront's LDS region, free (the claims are in registers).
 // `cold` = true: not decided here (the execution-order compare failed, so the hash table has to be asked; or a record
 // kind the table does not define) — the caller runs verify_table_one, and `loc` is to be ignored.
-__device__ __forceinline__ uint32_t verify_table_hot(const WitnessView& w, const EventClaimPacked& c, const TipsetCtxDev& tc,
-                                                     const uint8_t* __restrict__ blob, const ipcfp_trust_policy_t& trust,
-                                                     const ipcfp_event_filter_t& filter, bool has_filter, bool want_where,
-                                                     const void* safe, ValueLoc& loc, bool& cold) {
+__device__ __forceinline__ uint32_t verify_table_hot(const WitnessView& w, const EventClaimPacked& c, bool hot, const TipsetCtxDev& tc,
+                                                     const uint8_t* __restrict__ blob, uint64_t blob_len,
+                                                     const ipcfp_trust_policy_t& trust, const ipcfp_event_filter_t& filter,
+                                                     bool has_filter, bool want_where, const void* safe, uint8_t* region,
+                                                     uint32_t lane, ValueLoc& loc, bool& cold) {
     // ---- batch B: what the claim and the context's pointers address
     const EventCtxFacts f = event_ctx_facts(tc);
     Verdict v;
     event_prefix_rungs(v, c, f, trust);  // (registers only: the claim and the facts)
-    const bool pre_ok = !v.settled;
+    const bool pre_ok = hot && !v.settled;
     // (the two records that batch C hangs on go first: vmcnt counts in order, so they are waited for without the blob)
-    const bool tabulated = f.has_receipt_table && c.exec_index >= f.receipt_first && c.exec_index - f.receipt_first < f.n_receipt_leaves;
+    const bool tabulated = hot && f.has_receipt_table && c.exec_index >= f.receipt_first && c.exec_index - f.receipt_first < f.n_receipt_leaves;
     uint64_t rw[3];  // the ReceiptRec as words
     __builtin_memcpy(rw, guarded(tabulated, f.receipt_recs + (c.exec_index - f.receipt_first), safe), 24);
     const bool inv_ok = pre_ok && f.exec_inv && f.exec_keys && c.exec_index < f.exec_len;
     uint32_t inv;
     __builtin_memcpy(&inv, guarded(inv_ok, f.exec_inv + c.exec_index, safe), 4);
     const bool matchable = (c.flags & EC_DATA_MATCHABLE) != 0;  // hot_shape: then data_len == 32
-    const gbytes_t q0 = guarded(c.n_topics >= 1, blob + c.topics_off, safe);
-    const gbytes_t q1 = guarded(c.n_topics == 2, blob + c.topics_off + 33, safe);
-    const gbytes_t qd = guarded(matchable, blob + c.data_off, safe);
+    const bool rd0 = hot && c.n_topics >= 1, rd1 = hot && c.n_topics == 2, rdd = hot && matchable;
+    // the window: the extent of what the wavefront's usual claims read of the blob (claim_in_bounds has passed for each)
+    uint64_t lo, hi;
+    const bool reads = verify_window_lane(hot ? c.n_topics : 0u, c.topics_off, rdd, c.data_off, lo, hi);
+    const uint64_t start = verify_window_start(wave_min(reads ? uint32_t(lo) : 0xffffffffu));  // (lo is an offset: 32 bits)
+    const uint32_t win_len = __builtin_amdgcn_readfirstlane(
+        __any(reads) ? verify_window_len(start, wave_max(reads ? verify_window_rel_end(hi, start) : 0u), blob_len) : 0u);
     ClaimedBytes p;
-    p.flag[0] = q0[0];
-    p.topic[0][0] = ld16(q0 + 1);
-    p.topic[0][1] = ld16(q0 + 17);
-    p.flag[1] = q1[0];
-    p.topic[1][0] = ld16(q1 + 1);
-    p.topic[1][1] = ld16(q1 + 17);
-    p.data[0] = ld16(qd);
-    p.data[1] = ld16(qd + 16);
+    if (win_len) {  // (uniform) coalesced into the region, each lane's pieces out of it
+        stage_copy(region, blob + start, win_len, lane);
+        stage_publish();
+        const uint32_t j0 = rd0 ? uint32_t(c.topics_off - start) : 0u, j1 = rd1 ? j0 + 33u : 0u;
+        const uint32_t jd = rdd ? uint32_t(c.data_off - start) : 0u;
+        p.flag[0] = region[j0];
+        region_ld32(region, j0 + (rd0 ? 1u : 0u), p.topic[0]);
+        p.flag[1] = region[j1];
+        region_ld32(region, j1 + (rd1 ? 1u : 0u), p.topic[1]);
+        region_ld32(region, jd, p.data);
+    } else {  // entries too far apart for the window (or nothing to read): lane by lane from the blob
+        const gbytes_t q0 = guarded(rd0, blob + c.topics_off, safe);
+        const gbytes_t q1 = guarded(rd1, blob + c.topics_off + 33, safe);
+        const gbytes_t qd = guarded(rdd, blob + c.data_off, safe);
+        p.flag[0] = q0[0];
+        p.topic[0][0] = ld16(q0 + 1);
+        p.topic[0][1] = ld16(q0 + 17);
+        p.flag[1] = q1[0];
+        p.topic[1][0] = ld16(q1 + 1);
+        p.topic[1][1] = ld16(q1 + 17);
+        p.data[0] = ld16(qd);
+        p.data[1] = ld16(qd + 16);
+    }
     batch_end(rw[0], rw[1], rw[2], inv);
     const uint32_t rr_kind = uint32_t(rw[0]), rr_first = uint32_t(rw[0] >> 32), rr_block = uint32_t(rw[2]);
     const uint64_t rr_bitmap = rw[1];
@@ -209,8 +291,8 @@ __device__ __forceinline__ uint32_t verify_table_hot(const WitnessView& w, const
     const uint32_t slot = rr_first + uint32_t(__popcll(rr_bitmap & ((1ull << bit) - 1ull)));
     uint64_t ew[4];  // the EventRec as words: no field is ever indexed dynamically
     __builtin_memcpy(ew, guarded(have_event, f.event_recs + slot, safe), 32);
-    uint64_t block_off;
-    __builtin_memcpy(&block_off, guarded(want_where && have_event, w.off + rr_block, safe), 8);
+    uint64_t block_off = 0;
+    if (want_where) __builtin_memcpy(&block_off, guarded(have_event, w.off + rr_block, safe), 8);  // (uniform)
     batch_end(key.w[0], key.w[1], key.w[2], key.w[3], key.w[4]);
     batch_end(ew[0], ew[1], ew[2], ew[3], block_off);
 
@@ -267,11 +349,19 @@ __global__ __launch_bounds__(256) void k_verify_events_table(WitnessView w, cons
                                                              ipcfp_trust_policy_t trust, ipcfp_event_filter_t filter,
                                                              int has_filter, uint8_t* __restrict__ status,
                                                              ValueLoc* __restrict__ where) {
+    __shared__ __attribute__((aligned(16))) uint8_t regions[4][kStageStride];
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, first = t - lane;
+    if (first >= n) return;  // (a whole wavefront past the batch: nothing below waits for another wavefront)
     const bool live = t < n;
-    EventClaimPacked c;
-    if (live) c = claims[t];
-    else c.context = 0;
+    // the wavefront's claims, [claims + first, claims + first + min(64, n - first)), as one byte range through its region
+    uint8_t* const region = regions[threadIdx.x >> 6];
+    stage_copy(region, reinterpret_cast<const uint8_t*>(claims + first), min(64u, n - first) * uint32_t(sizeof(EventClaimPacked)), lane);
+    stage_publish();
+    EventClaimPacked c{};
+    // (104·lane is 8-aligned: 64-bit reads, none off its natural alignment)
+    if (live) __builtin_memcpy(&c, __builtin_assume_aligned(region + lane * sizeof(EventClaimPacked), 8), sizeof c);
+    stage_publish();  // (the region is written again below: every lane's claim is out of it first)
     ValueLoc loc{kNoBlock, 0, 0};
     uint32_t st = IPCFP_ST_ERR_BAD_CLAIM;
     const bool inb = live && claim_in_bounds(c, n_ctxs, blob_len);
@@ -280,16 +370,19 @@ __global__ __launch_bounds__(256) void k_verify_events_table(WitnessView w, cons
     const uint32_t ctx0 = __builtin_amdgcn_readfirstlane(inb ? c.context : 0xffffffffu);
     bool cold = inb;  // lanes that take the ladder of early returns
     if (ctx0 != 0xffffffffu && __all(!inb || c.context == ctx0)) {
-        if (inb && hot_shape(c)) {
+        const bool hot = inb && hot_shape(c);
+        if (__any(hot)) {  // every lane goes in (the window is carried by all 64); only the hot ones come out with a verdict
             ValueLoc hot_loc;
             bool again;
-            const uint32_t hot_st = verify_table_hot(w, c, ctxs[ctx0], blob, trust, filter, has_filter != 0, where != nullptr,
-                                                     claims + t, hot_loc, again);
-            st = again ? st : hot_st;
-            loc.block = again ? loc.block : hot_loc.block;
-            loc.off = again ? loc.off : hot_loc.off;
-            loc.len = again ? loc.len : hot_loc.len;
-            cold = again;
+            // (`safe`: one address for the wavefront — its first claim — so that a guarded-off load touches one line)
+            const uint32_t hot_st = verify_table_hot(w, c, hot, ctxs[ctx0], blob, blob_len, trust, filter, has_filter != 0,
+                                                     where != nullptr, claims + first, region, lane, hot_loc, again);
+            const bool keep = !hot || again;
+            st = keep ? st : hot_st;
+            loc.block = keep ? loc.block : hot_loc.block;
+            loc.off = keep ? loc.off : hot_loc.off;
+            loc.len = keep ? loc.len : hot_loc.len;
+            cold = hot ? again : cold;
         }
     }
     // Everything else — a claim that needs the hash-table probe, more than two topics, data of another length, contexts
