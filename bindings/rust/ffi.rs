@@ -470,6 +470,31 @@ impl Witness<'_> {
         String::from_utf8(text).map_err(|e| anyhow!("ipcfp_bundle_write_json: {e}"))
     }
 
+    /// The same text for the proofs the generators left in HBM (`generate_proof_bundle`, src/proofs/generator.rs, then
+    /// `serde_json::to_string`, src/proofs/common/bundle.rs:39-45) without a claim ever becoming a host string: the claims
+    /// head is written on the device as well.  `None` / null: an empty list.  A refusal names the list (0 storage, 1 events,
+    /// 2 blocks) and the lowest offending index in the error text.
+    ///
+    /// # Safety
+    /// `events` is null or a live handle of `ipcfp_generate_event_claims*` made on this engine.
+    pub unsafe fn generated_bundle_to_json(&self, storage: Option<&GeneratedStorageClaims>, events: *mut ipcfp_generated_events_t,
+                                           block_ids: Option<&[u32]>) -> Result<String> {
+        let gs = storage.map_or(std::ptr::null_mut(), |s| s.raw);
+        let (ids, n_ids) = match block_ids {
+            Some(v) => (v.as_ptr(), v.len() as u64),
+            None => (std::ptr::null(), ipcfp_witness_block_count(self.raw())),
+        };
+        let (mut len, mut kind, mut bad) = (0u64, -1i32, u64::MAX);
+        let rc = ipcfp_bundle_write_generated_json(self.eng.ctx, self.raw(), gs, events, ids, n_ids, std::ptr::null_mut(), 0, &mut len,
+                                                   &mut kind, &mut bad);
+        if rc != 0 { return Err(self.eng.err("ipcfp_bundle_write_generated_json", rc)); }
+        let mut text = vec![0u8; len as usize];
+        let rc = ipcfp_bundle_write_generated_json(self.eng.ctx, self.raw(), gs, events, ids, n_ids, text.as_mut_ptr() as *mut c_char, len,
+                                                   &mut len, &mut kind, &mut bad);
+        if rc != 0 { return Err(self.eng.err("ipcfp_bundle_write_generated_json", rc)); }
+        String::from_utf8(text).map_err(|e| anyhow!("ipcfp_bundle_write_generated_json: {e}"))
+    }
+
     /// drop-in for `verify_storage_proof` over all storage proofs of a bundle (src/proofs/storage/verifier.rs:24-63;
     /// the loop of src/proofs/verifier.rs:19-28 — the witness is NOT rebuilt per proof).
     pub fn verify_storage_proof(&self, proofs: &[StorageProof], trust: &ipcfp_trust_policy_t) -> Result<Vec<bool>> {

@@ -193,7 +193,8 @@ enum {
     IPCFP_K_SCAN_MULTI_TAIL = 24,  /* … the table route's tail in one launch: look-back prefix sum, map, fill, counts, mailbox */
     IPCFP_K_SCAN_TIPSETS = 25,     /* ipcfp_scan_events_tipsets*: tipset boundaries, PASS 1 / PASS 2 over the leaves of a chain */
     IPCFP_K_GEN_TIPSETS = 26,      /* ipcfp_generate_event_claims_tipsets: chain prologue, segmented execution order, gather, marks, patch */
-    IPCFP_K_COUNT = 27
+    IPCFP_K_CLAIM_TEXT = 27,       /* ipcfp_bundle_write_packed_json: per-run fragments, claim text sizes, the head's text */
+    IPCFP_K_COUNT = 28
 };
 int ipcfp_profile_enable(ipcfp_ctx_t* ctx, int on);
 int ipcfp_profile_reset(ipcfp_ctx_t* ctx);
@@ -1256,6 +1257,41 @@ int ipcfp_bundle_write_json(ipcfp_ctx_t* ctx, ipcfp_witness_t* w,
                             const ipcfp_event_proof_t* events, uint64_t n_events,
                             const uint32_t* block_ids, uint64_t n_blocks,
                             char* out, uint64_t cap, uint64_t* len);
+
+/* ---- the same text from PACKED claims resident in HBM: the claims head written on the device too ----------------------
+ * What `serde_json::to_string(&UnifiedProofBundle)` (src/proofs/common/bundle.rs:39-45) gives for the proofs
+ * `generate_proof_bundle` collects (src/proofs/generator.rs), without a claim ever existing as a host string: every
+ * character of a generated claim's text is a function of the packed fields, and the head is written by kernels into the
+ * device text buffer the block writer fills, ahead of the blocks; one copy brings the whole text back.
+ *   storage claims   the column form, DEVICE pointers, under the alignment rules of ipcfp_verify_storage_columns_device
+ *   event claims     a HOST tipset table, DEVICE claims (8-byte aligned) and blob, as ipcfp_verify_event_claims_device
+ *   block_ids, out / cap / *len   exactly as ipcfp_bundle_write_json (sizing call, exact *len, nothing written on a short cap)
+ * The text is byte for byte ipcfp_bundle_write_json of ipcfp_unpack_storage_claims(ipcfp_expand_storage_claims(columns))
+ * and ipcfp_unpack_event_claims(tipsets, claims, blob) with the same block_ids, and the refusals are those of that route,
+ * with its return code and its lowest offending index: storage is judged before events, events before blocks.
+ * *bad_kind (nullable; 0: storage, 1: events, 2: blocks; -1: none) and *bad_index (nullable; UINT64_MAX: none) name it, as
+ * does ipcfp_last_error.  Nothing is written after a refusal.
+ *   IPCFP_E_INVALID      a run table that does not tile [0, n_storage) (kind 0, no index); a run with a flag bit outside
+ *                        IPCFP_SRUN_FLAG_MASK | IPCFP_SCOL_FLAG_MASK or a reserved word that is not 0 (the run's first claim);
+ *                        a claim whose run flags | cflags byte are not exactly those six bits — the expanded claim is what
+ *                        the host route judges, so a run that lacks a bit its claims bring is sound; a CID slot that is not
+ *                        one well-formed CID; an event claim with
+ *                        tipset >= n_tipsets, without IPCFP_CLAIM_MSG_PARSED | IPCFP_CLAIM_DATA_MATCHABLE, whose blob ranges
+ *                        leave blob_len, with a topic flag byte of 0, or naming a tipset whose parsed flags are not both set
+ *   IPCFP_E_UNSUPPORTED  a folded slot (0xff …) where a string is needed; n_storage + n_events >= 2^32 - 4
+ * A tipset that no claim names is never judged. */
+int ipcfp_bundle_write_packed_json(ipcfp_ctx_t* ctx, ipcfp_witness_t* w,
+                                   const void* runs_d, uint32_t n_runs, const void* slot_d, const void* value_d,
+                                   const void* cflags_d, uint64_t n_storage,
+                                   const ipcfp_tipset_ref_t* tipsets, uint32_t n_tipsets, const void* claims_d,
+                                   uint64_t n_events, const void* blob_d, uint64_t blob_len,
+                                   const uint32_t* block_ids, uint64_t n_blocks,
+                                   char* out, uint64_t cap, uint64_t* len, int* bad_kind, uint64_t* bad_index);
+/* … fed from the generators' handles: their own device pointers and the events handle's _tipsets.  A NULL handle is an empty
+ * list.  A storage handle with a failing spec is refused (IPCFP_E_INVALID) at its _first_error, as its _proofs is. */
+int ipcfp_bundle_write_generated_json(ipcfp_ctx_t* ctx, ipcfp_witness_t* w, ipcfp_generated_storage_claims_t* gs,
+                                      ipcfp_generated_events_t* ge, const uint32_t* block_ids, uint64_t n_blocks,
+                                      char* out, uint64_t cap, uint64_t* len, int* bad_kind, uint64_t* bad_index);
 
 #ifdef __cplusplus
 } /* extern "C" */

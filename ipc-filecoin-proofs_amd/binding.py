@@ -109,6 +109,7 @@ KERNEL_IDS = {
     "scan_multi_tail": 24,
     "scan_tipsets": 25,
     "gen_tipsets": 26,
+    "claim_text": 27,
 }
 
 MAX_SCAN_SPECS = 1024
@@ -435,6 +436,10 @@ def load_library() -> C.CDLL:
         "ipcfp_unpacked_storage_destroy": (None, [vp]),
         "ipcfp_bundle_write_claims_json": (i32, [vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
         "ipcfp_bundle_write_json": (i32, [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]),
+        "ipcfp_bundle_write_packed_json": (i32, [vp, vp, vp, C.c_uint32, vp, vp, vp, u64, vp, C.c_uint32, vp, u64, vp, u64, vp, u64,
+                                                 vp, u64, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(u64)]),
+        "ipcfp_bundle_write_generated_json": (i32, [vp, vp, vp, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_int),
+                                                    C.POINTER(u64)]),
         "ipcfp_scan_events_multi": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
         "ipcfp_scan_events_multi_device": (i32, [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
         "ipcfp_scan_events_tipsets": (i32, [vp, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, u64, C.POINTER(u64), vp, vp, u64, C.POINTER(u64), vp, vp]),
@@ -525,6 +530,65 @@ class Engine:
         ms = C.c_double()
         self._check(self.lib.ipcfp_profile_read(self.h, KERNEL_IDS[kernel], C.byref(n), C.byref(ms)), "profile_read")
         return n.value, ms.value
+
+    # -- a bundle's JSON text from packed claims resident in HBM ---------------------------------
+    def _bundle_write_packed(self, what, call, cap):
+        """The two-call buffer contract around `call(out, cap, len, bad_kind, bad_index)`.  cap None: sizing call, then
+        a buffer of exactly that size → the text; an int: ONE call with that capacity → (rc, len, buffer).
+        A refusal raises EngineError with `.rc`, `.bad_kind` (0 storage, 1 events, 2 blocks) and `.bad_index` (None: no index)."""
+        n, kind, bad = C.c_uint64(), C.c_int(), C.c_uint64()
+
+        def check(rc):
+            if rc != 0:
+                msg = self.lib.ipcfp_last_error(self.h)
+                e = EngineError(f"{what}: {msg.decode() if msg else ''} ({rc})")
+                e.rc, e.bad_kind, e.bad_index = rc, int(kind.value), (None if bad.value == 2**64 - 1 else int(bad.value))
+                raise e
+
+        if cap is not None:
+            out = np.full(max(int(cap), 1), 0xA5, dtype=np.uint8)
+            rc = call(_p(out) if cap else None, int(cap), C.byref(n), C.byref(kind), C.byref(bad))
+            return int(rc), int(n.value), out[: int(cap)]
+        check(call(None, 0, C.byref(n), C.byref(kind), C.byref(bad)))
+        out = np.empty(max(int(n.value), 1), dtype=np.uint8)
+        check(call(_p(out), int(n.value), C.byref(n), C.byref(kind), C.byref(bad)))
+        return out[: int(n.value)].tobytes()
+
+    def bundle_write_packed_json(self, witness, runs_ptr: int, n_runs: int, slot_ptr: int, value_ptr: int, cflags_ptr: int,
+                                 n_storage: int, tipsets, claims_ptr: int, n_events: int, blob_ptr: int, blob_len: int,
+                                 block_ids=None, cap=None):
+        """`serde_json::to_string(&UnifiedProofBundle)` of packed claims resident in HBM (ipcfp_bundle_write_packed_json): the
+        storage claims in column form and the event claims + blob as DEVICE addresses, `tipsets` a host TIPSET_DTYPE array,
+        the listed blocks of `witness` (None: every block in id order).  The claims head is written on the device."""
+        ts = np.ascontiguousarray(tipsets, dtype=TIPSET_DTYPE) if tipsets is not None else np.zeros(0, dtype=TIPSET_DTYPE)
+        if block_ids is None:
+            ids, nb = None, witness.n
+        else:
+            ids = np.ascontiguousarray(block_ids, dtype=np.uint32)
+            nb = len(ids)
+
+        def call(out, cap_, n, kind, bad):
+            return self.lib.ipcfp_bundle_write_packed_json(
+                self.h, witness.h, runs_ptr or None, int(n_runs), slot_ptr or None, value_ptr or None, cflags_ptr or None,
+                int(n_storage), _p(ts) if len(ts) else None, len(ts), claims_ptr or None, int(n_events), blob_ptr or None,
+                int(blob_len), _p(ids), nb, out, cap_, n, kind, bad)
+
+        return self._bundle_write_packed("bundle_write_packed_json", call, cap)
+
+    def bundle_write_generated_json(self, witness, gs, ge, block_ids=None, cap=None):
+        """The same fed from the generators' handles (GeneratedStorageClaims / GeneratedEvents; None: an empty list):
+        ipcfp_bundle_write_generated_json."""
+        if block_ids is None:
+            ids, nb = None, witness.n
+        else:
+            ids = np.ascontiguousarray(block_ids, dtype=np.uint32)
+            nb = len(ids)
+
+        def call(out, cap_, n, kind, bad):
+            return self.lib.ipcfp_bundle_write_generated_json(self.h, witness.h, gs.h if gs is not None else None,
+                                                              ge.h if ge is not None else None, _p(ids), nb, out, cap_, n, kind, bad)
+
+        return self._bundle_write_packed("bundle_write_generated_json", call, cap)
 
     # -- batch hashes ------------------------------------------------------------
     def _hash(self, fn, data, off, lens):

@@ -265,6 +265,32 @@ int launch_bundle_write_text(ipcfp_ctx* ctx, const uint32_t* ids_d, uint32_t n, 
                              const void* pos_d, const uint64_t* text_off_d, const uint32_t* unit0_d, uint32_t n_units,
                              uint8_t* text_d);
 
+// --- claim_text.hip --- the claims head of a bundle's JSON text out of packed claims in HBM (host/bundle_write_packed.cpp)
+constexpr uint32_t kClaimTextRunFragStride = 448;  // bytes of run_frag_d per run
+constexpr uint32_t kClaimTextRunInfo = 8;          // bytes of run_info_d per run
+constexpr uint32_t kClaimTextTipsetRec = 16;       // tipsets_d: {u64 offset into tipset_frag_d, u32 length, u32 refusal code (0, 7: invalid, 8: folded)}
+struct ClaimTextIn {
+    StorageColumnsDev cols;    // the storage claims
+    uint32_t n_storage;
+    const uint32_t* run_of_d;  // launch_storage_column_runs over n_storage words preset to 0xff
+    void* run_info_d;          // scratch: n_runs × kClaimTextRunInfo
+    uint8_t* run_frag_d;       // scratch: n_runs × kClaimTextRunFragStride
+    const void* claims_d;      // EventClaimPacked[n_events]
+    uint32_t n_events;
+    const uint8_t* blob_d;
+    uint64_t blob_len;
+    const void* tipsets_d;     // n_tipsets records of kClaimTextTipsetRec
+    const uint8_t* tipset_frag_d;
+    uint32_t n_tipsets;
+};
+// per-run fragments, then one lane per item (n_storage + n_events + 3: the three literals of the head are items): checks and
+// text sizes into size_d, their exclusive prefix into off_d, *total_d = the head's length.  *first_bad_d (0xff… before) = min
+// over (kind << 36 | claim index << 4 | code), kind 0: storage, 1: events; scratch_d: div_up(items, 1024) + 1 u64
+int launch_claim_text_sizes(ipcfp_ctx* ctx, const ClaimTextIn& in, uint64_t* size_d, uint64_t* off_d, uint64_t* total_d,
+                            uint64_t* scratch_d, unsigned long long* first_bad_d);
+// the head_len bytes of the head at text_d (16-byte aligned); only behind a sizing pass that refused nothing
+int launch_claim_text_write(ipcfp_ctx* ctx, const ClaimTextIn& in, const uint64_t* off_d, uint64_t head_len, uint8_t* text_d);
+
 // --- generate.hip ---
 int launch_generate_storage(ipcfp_ctx* ctx, const WitnessView& w, const CidKey& child, const void* specs_d, uint32_t n,
                             void* out_d);
