@@ -320,7 +320,8 @@ int launch_sgen_specs(ipcfp_ctx* ctx, const WitnessView& w, const void* table_d,
 int launch_sgen_run_records(ipcfp_ctx* ctx, const void* runs_d, uint32_t n_runs, uint32_t n, const CidKey& child, long long child_epoch,
                             const uint64_t* actor_id_d, void* out_d);
 // --- storage_claims_gen_tipsets.inc (part of storage_claims_gen.hip) --- the same for ONE spec list at each of n_tipsets
-// children.  `w`: the view whose `touched` is row 0 of the recorder, n_tipsets rows of `words` words; runs0_d / run_of0_d:
+// children: the kernels above instantiated over SgenChain instead of SgenOne (storage_claims_gen_body.h), behind
+// k_sgent_heads and k_sgent_run_init, and the cut.  `w`: the view whose `touched` is row 0 of the recorder, n_tipsets rows of `words` words; runs0_d / run_of0_d:
 // launch_storage_run_heads over the n_specs-entry list (n_runs0 runs); runs_d: StorageRun[n_tipsets * n_runs0], run (t, r) at
 // t * n_runs0 + r; claim (t, s) at t * n_specs + s
 // heads_d (96 bytes per tipset): child header → parent_state_root → StateRoot.actors once per tipset, then every run from it
